@@ -61,6 +61,22 @@ Objects on the JSON line — every number is measured in this run unless its key
   vae / e2e    — AutoencoderKL decode frames/s; a whole video (50-step ddim_sample_loop + 16-frame decode).
 
 `model_tflops_per_s` / `frac_of_mfma_peak` count the REFERENCE's work per step (2 forwards x 8.665 TFLOP).
+
+A plain run (no `--full`) does only what the headline needs: set up, warm up, time `--steps` steps, write the outputs of
+the last step if `--dump-outputs DIR` is given, print the line.  Everything else above — parity, calibration.packed_digest,
+scaling_model, roofline / hbm_kernels, vae / e2e, variants, cpu_baseline — is measured with `--full` only:
+
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
+
+Calibration cache: with `--precision calibrated` on a GPU the timed model's calibrated weights are read from
+`_cache/calibration/` when a file for the same weights, shapes, sources, libraries and device is there (the pass is a pure
+function of those), else calibrated here and saved there — `__graft_entry__.build()` fills it on a GPU box, so a plain run
+does not pay the pack-time pass.  `--no-calibration-cache` calibrates in the process as before; `calibration.loaded_from`
+on the line names the file that was used.
+
+`--dump-outputs DIR`: DIR/<name>.npy (float32) of what the timed path returned in its last timed step — for the t2v
+family `x_prev` and `x0` of `DiffusionDDIM.ddim_sample` — so two builds can be compared output for output on the same
+seeded inputs.
 """
 from __future__ import annotations
 
@@ -288,6 +304,77 @@ def golden_parity(model, gold, dev):
     return float((out - ref).norm() / ref.norm())
 
 
+CAL_CACHE = os.path.join(ROOT, "_cache", "calibration")
+
+
+def calibration_cache_path(name, dtype, dev, weights):
+    """The cache file of the calibrated weights of config `name` in `dtype` on `dev`, or None off the GPU.  Its name carries a
+    digest of everything the deterministic pass reads: the weights (`weights`: how they are made), the config's shapes, the
+    package and kernel sources, this script, the loaded libraries, torch, the LAPACK thread count and the device — any change
+    gives another file, so a cached result is only ever reused where the pass would compute the same bits again."""
+    import hashlib
+    if torch.device(dev).type != "cuda":
+        return None
+    from vgen_amd import calibrate, lib
+    h = hashlib.sha256()
+    c = CONFIGS[name]
+    h.update(repr((name, dtype, weights, c["cls"], sorted(c["cfg"].items()), c["latent"], c.get("comps"), torch.__version__,
+                   max(1, min(os.cpu_count() or 1, calibrate.CALIBRATION_THREADS)),
+                   torch.cuda.get_device_properties(dev).gcnArchName)).encode())
+    files = [os.path.abspath(__file__), lib.LIB_PATH, os.path.join(ROOT, "vgen_amd", "libvgen_host.so")]
+    for sub in ("vgen_amd", os.path.join("vgen_amd", "csrc"), "include"):
+        d = os.path.join(ROOT, sub)
+        files += [os.path.join(d, f) for f in sorted(os.listdir(d))
+                  if f.endswith((".py", ".hip", ".cpp", ".h", ".inc"))]
+    for f in files:
+        if os.path.exists(f):
+            h.update(f.encode())
+            with open(f, "rb") as fh:
+                h.update(fh.read())
+    return os.path.join(CAL_CACHE, f"{name}_{dtype}_{h.hexdigest()[:20]}.cal")
+
+
+def save_calibration(model, path, prune_prefix=None):
+    """save_calibrated to `path` through a temporary file (a run cut short leaves no partial file behind); prune_prefix: older
+    cache files of the same config and dtype are removed.  A failure to write is reported, not raised: the run goes on."""
+    from vgen_amd.calibrate import save_calibrated
+    tmp = f"{path}.{os.getpid()}.tmp"
+    try:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        save_calibrated(model, tmp)
+        os.replace(tmp, path)
+    except OSError as exc:
+        print(f"bench.py: could not save {path} ({exc})", file=sys.stderr)
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        return
+    if prune_prefix:
+        d = os.path.dirname(path)
+        for f in os.listdir(d):
+            if f.startswith(prune_prefix) and f.endswith(".cal") and os.path.join(d, f) != path:
+                os.remove(os.path.join(d, f))
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy of each tensor in `arrays` (float32; float64 stays float64), at most DUMP_BYTES in all: a tensor over its
+    share is written as a fixed strided sample of its flattened elements (every k-th, from the first), `<name>.npy` then
+    holding the sample — the same elements in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_BYTES - (1 << 20)) // max(len(arrays), 1)          # 1 MiB left for the .npy headers and rounding
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        flat = t.reshape(-1)
+        if flat.numel() * flat.element_size() > share:
+            step = -(-flat.numel() * flat.element_size() // share)
+            t = flat[::step]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+
+
 class StepTimer:
     """Times `steps` calls of the public per-step sampler API (after 2 setup calls and `warmup` calls)."""
 
@@ -300,8 +387,9 @@ class StepTimer:
         return self.t_bufs[self.steps_all[i % len(self.steps_all)]]
 
     def step(self, xt, i):
-        return self.diff.ddim_sample(xt, self.t_of(i), self.model, self.mkw, guide_scale=self.guide, ddim_timesteps=50,
-                                     eta=0.0)[0]
+        self.last = self.diff.ddim_sample(xt, self.t_of(i), self.model, self.mkw, guide_scale=self.guide, ddim_timesteps=50,
+                                          eta=0.0)         # (x_{t-1}, x0): what a caller of the step receives
+        return self.last[0]
 
     def run(self, steps, warmup, world=1):
         import torch.distributed as dist
@@ -534,6 +622,8 @@ def run_videolcm(args, dev, model, world, rank):
     torch.cuda.synchronize()
     dt_s = time.perf_counter() - t0
     steps = 4 * nvid
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latent": lat, "video": vid})
     return {
         "metric": "denoise_steps_per_sec", "value": round(steps / dt_s, 4), "unit": "steps/s", "n_gpus": world,
         "steps": steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt_s / steps, 3), "higher_is_better": True,
@@ -617,6 +707,8 @@ def run_two_stage(args, dev, world, rank):
     video = vae.decode_video(out * 0.2, scale_factor=0.18215, decoder_bs=4)
     t0 = lap("stage2_decode_s", t0)
     total = time.perf_counter() - t_all - build_s
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latent": out, "video": video})
     return {
         "metric": "frames_per_sec_end_to_end", "value": round(F / total, 4), "unit": "frames/s", "n_gpus": world,
         "steps": n1 + 2 * n2, "warmup": 0, "ms_per_step": round(1e3 * total / (n1 + 2 * n2), 3), "higher_is_better": True,
@@ -658,7 +750,16 @@ def main():
     ap.add_argument("--calibration-file", default=None,
                     help="--precision calibrated: load the timed model's calibrated weights from this file if it exists, else "
                          "calibrate and save them there (calibrate.save_calibrated) — profiling passes of one model pay the "
-                         "pack-time pass once")
+                         "pack-time pass once.  Default on a GPU: a file of the calibration cache (_cache/calibration/)")
+    ap.add_argument("--no-calibration-cache", action="store_true",
+                    help="--precision calibrated without --calibration-file: calibrate in this process, read and write no cache")
+    ap.add_argument("--prepare-only", action="store_true",
+                    help="build (and calibrate, filling the calibration cache) the timed model, then exit: nothing is timed")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: parity, packed digest, scaling model, roofline, VAE / "
+                         "e2e, variants, CPU baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32, <= 64 MB)")
     ap.add_argument("--stage1", default="text_image", choices=["text_image", "vcomposer"],
                     help="--config tft2v_sr600: composition list of the first stage (vcomposer = the reference yaml's eight "
                          "entries with six pixel-resolution condition maps)")
@@ -744,8 +845,12 @@ def main():
         # the golden fixture's weights: shapes + seed -> the tensors the reference's fp32 forward was recorded on
         gold = torch.load(GOLDEN_T2V, map_location="cpu", weights_only=False)
         sd = seeded_state_dict(gold["shapes"], seed=gold["seed"])
-    cal_file = None
-    if world > 1 and args.precision == "calibrated":
+    cal_file = cache_prefix = None
+    if args.precision == "calibrated" and args.calibration_file is None and not args.no_calibration_cache:
+        weights = (gold["seed"], sorted(gold["shapes"].items())) if gold is not None else "randomize_ seed 0"
+        args.calibration_file = calibration_cache_path(args.config, args.dtype, dev, weights)
+        cache_prefix = f"{args.config}_{args.dtype}_"
+    if world > 1 and args.precision == "calibrated" and not (args.calibration_file and os.path.exists(args.calibration_file)):
         # the persistent route (calibrate.save_calibrated / precision="calibrated", calibration=<file>): ONE rank pays the
         # pack-time pass, the others load its result — the same bits either way (the pass is deterministic)
         import tempfile
@@ -773,10 +878,12 @@ def main():
             model = build_model(args.config, dev, args.dtype, "calibrated", state_dict=sd, calibration=args.calibration_file)
         else:
             model = build_model(args.config, dev, args.dtype, "calibrated", state_dict=sd)
-            from vgen_amd.calibrate import save_calibrated
-            save_calibrated(model, args.calibration_file)
+            save_calibration(model, args.calibration_file, cache_prefix)
     else:
         model = build_model(args.config, dev, args.dtype, args.precision, state_dict=sd)
+    if args.prepare_only:
+        _finish(None, world)
+        return
     if args.config == "t2v":
         drop_masters(model, dev)
     if args.config == "videolcm":
@@ -835,11 +942,16 @@ def main():
         timer = StepTimer(diff, model, xt0, mkw, guide, dev, P)
         api = "GaussianDiffusion.sample(solver='dpmpp_2m_sde', steps=K) — K CFG model evaluations + solver updates, whole loop timed"
         cache = srd.forward_diffusion.sessions
+        outputs = {"x_sample": xt}
     else:
         timer = StepTimer(diff, model, xt0, mkw, guide, dev, P)
         dt_s, xt = timer.run(args.steps, args.warmup, world)
         api = "DiffusionDDIM.ddim_sample per step (public sampler API; cached sampling session underneath)"
         cache = part.sessions if part is not None else diff.sessions
+        outputs = {"x_prev": timer.last[0], "x0": timer.last[1]}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+    del outputs
     finite = bool(torch.isfinite(xt).all())
     xt_absmax = float(xt.float().abs().nan_to_num(nan=float("inf")).max())
     sess = None
@@ -885,12 +997,12 @@ def main():
         res["inversion"] = inversion
     if getattr(model, "bench_calibration", None) is not None:
         res["calibration"] = dict(model.bench_calibration)
-        if rank == 0 and world == 1 and args.config == "t2v":
+        if args.full and rank == 0 and world == 1 and args.config == "t2v":
             from vgen_amd.calibrate import packed_digest
             res["calibration"]["packed_digest"] = packed_digest(model)[:16]
 
     # ---- parity of the model that was just timed, computed here --------------------------------------------
-    if rank == 0 and gold is not None and not args.no_parity:
+    if args.full and rank == 0 and gold is not None and not args.no_parity:
         fx = {FIXTURE_NAMES[0]: golden_parity(model, gold, dev)}
         if os.path.exists(GOLDEN_T2V_C):
             gc_ = torch.load(GOLDEN_T2V_C, map_location="cpu", weights_only=False)
@@ -923,7 +1035,7 @@ def main():
     # A unit-major rank runs ONE unit's forward + the update; the pair step above runs two units in one batch.  Their ratio
     # bounds the strong scaling of a single video on 2 GPUs before any collective cost; weak scaling (P = N prompts, what
     # --gpus N measures) keeps whole pairs per rank.  No 1 -> 8 curve has been measured on hardware (the driver's to run).
-    if rank == 0 and world == 1 and part is None and args.config == "t2v" and G == 2 and not args.no_scaling_model:
+    if args.full and rank == 0 and world == 1 and part is None and args.config == "t2v" and G == 2 and not args.no_scaling_model:
         from vgen_amd.session import SessionCache
         sc = SessionCache(capacity=1)
         s1 = sc.get(model, tuple(xt0.shape), dev, list(kw), torch.long, 1000, units=[0])
@@ -950,14 +1062,14 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- roofline of the dominant kernel (instrumented eager pass, same step) ----------------------
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         try:
             res.update(roofline_pass(args, model, timer, xt0, kw, G, guide, args.precision))
         except Exception as exc:                                # noqa: BLE001 — an instrumentation failure must not cost the line
             res["roofline"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
 
     # ---- VAE decode frames/s + a whole video end to end --------------------------------------------------
-    if rank == 0 and not args.no_vae:
+    if args.full and rank == 0 and not args.no_vae:
         from vgen_amd.vae import AutoencoderKL
         fh, fw = (int(v) for v in args.vae_size.split("x"))
         vae = build_vae(dev, args.dtype, args.precision)
@@ -1057,7 +1169,7 @@ def main():
         del vae
 
     # ---- the other modes, same measurements (timed steps + parity), after the headline ------------------------------------
-    if rank == 0 and world == 1 and part is None and args.config == "t2v" and args.variants:
+    if args.full and rank == 0 and world == 1 and part is None and args.config == "t2v" and args.variants:
         res["variants"] = {}
         del model, timer, sess
         diff.sessions.clear()
@@ -1100,7 +1212,7 @@ def main():
     # the fp32 torch forward slower on the 256-core host (363 s per forward with 256 threads in an earlier run).
     # With the reference tree present (the build container) the forward is the REFERENCE's own UNetSD_T2VBase through
     # oracle/ref_import.py (kind "reference"); on the GPU box, which has no /root/reference, the port (oracle/torch_ref.py).
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "t2v":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "t2v":
         from oracle import ref_import, torch_ref
         cores = min(os.cpu_count() or 1, 32)
         torch.set_num_threads(cores)

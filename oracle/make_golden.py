@@ -743,6 +743,89 @@ def make_yardstick(R, full):
     json.dump(old, open(path, "w"), indent=1)
 
 
+SCHEDULE_CASES = [("cosine", dict(cosine_s=0.008)), ("cosine", dict(cosine_s=0.008, zero_terminal_snr=True)),
+                  ("linear_sd", dict(init_beta=0.00085, last_beta=0.012)),
+                  ("linear", dict(init_beta=0.0001, last_beta=0.02)),
+                  ("quadratic", dict(init_beta=0.001, last_beta=0.02, zero_terminal_snr=True))]
+
+
+def make_live_reference(R):
+    """live_reference.pt: the reference's side of the tests that used to import it at test time (test_oracle, test_gauss,
+    test_schedules) — the shapes of its modules, the seeded inputs and its outputs, so those tests run anywhere."""
+    U, G = R["util"], R["diffusion_gauss"]
+    out = {}
+    with torch.no_grad():
+        ref = R["MODEL"].build(dict(type="UNetSD_T2VBase", **UNET_TINY)).eval()
+        shapes = torch_ref.shapes_of(ref)
+        ref.load_state_dict(torch_ref.synth_state_dict(shapes, seed=7), strict=True)
+        g = torch.Generator().manual_seed(3)
+        x = torch.randn(1, 4, 3, 8, 8, generator=g)        # odd frame count, other resolution
+        y = torch.randn(1, 5, 1024, generator=g)           # short context
+        t = torch.tensor([37])
+        out["unet"] = dict(shapes=shapes, seed=7, x=x, y=y, t=t, out=ref(x, t, y=y))
+
+        def synth(m, seed):
+            sh = torch_ref.shapes_of(m)
+            m.load_state_dict(torch_ref.synth_state_dict(sh, seed=seed), strict=True)
+            return sh
+        g = torch.Generator().manual_seed(0)
+        rb = U.ResBlock(128, 256, 0.1, out_channels=64, use_scale_shift_norm=False).eval()
+        sh = synth(rb, 1)
+        x, e = torch.randn(6, 128, 5, 7, generator=g), torch.randn(6, 256, generator=g)
+        out["resblock"] = dict(shapes=sh, seed=1, x=x, e=e, out=rb(x, e, 2))
+        st = U.SpatialTransformer(128, 2, 64, depth=1, context_dim=96, use_linear=True).eval()
+        sh = synth(st, 2)
+        x, c = torch.randn(3, 128, 4, 5, generator=g), torch.randn(3, 9, 96, generator=g)
+        out["spatial"] = dict(shapes=sh, seed=2, x=x, c=c, out=st(x, c))
+        tt = U.TemporalTransformer(64, 2, 64, depth=1, context_dim=96).eval()      # inner 128 != 64
+        sh = synth(tt, 3)
+        x = torch.randn(2, 64, 6, 3, 4, generator=g)
+        out["temporal"] = dict(shapes=sh, seed=3, x=x, out=tt(x))
+
+        vae = R["AUTO_ENCODER"].build(dict(type="AutoencoderKL", ddconfig=VAE_TINY, embed_dim=4)).eval()
+        sh = synth(vae, 4)
+        g = torch.Generator().manual_seed(1)
+        z = torch.randn(1, 4, 6, 10, generator=g)
+        img = torch.randn(1, 3, 48, 80, generator=g)
+        out["vae"] = dict(shapes=sh, seed=4, z=z, decode=vae.decode(z), img=img, moments=vae.encode(img).parameters)
+        diff = R["DIFFUSION"].build(dict(type="DiffusionDDIM", **DDIM_T2V))
+        noise = torch.randn(1, 4, 2, 4, 4, generator=g)
+        kw = [dict(y=torch.randn(1, 3, 8, generator=g)), dict(y=torch.randn(1, 3, 8, generator=g))]
+        out["ddim_loop"] = dict(betas=diff.betas, noise=noise, kw=kw,
+                                out=diff.ddim_sample_loop(noise.clone(), dummy_model, kw, guide_scale=7.5, ddim_timesteps=25,
+                                                          eta=0.0))
+
+    # DPM-Solver++(2M) SDE at eta = 1 with the reference's Brownian sampler (the deterministic torchsde stand-in of
+    # oracle/ref_import.py): its output and every noise draw with its interval, in call order, for a replaying sampler
+    draws = []
+
+    class Recording(G.BrownianTreeNoiseSampler):
+        def __call__(self, sigma, sigma_next):
+            w = super().__call__(sigma, sigma_next)
+            draws.append((float(sigma), float(sigma_next), w.clone()))
+            return w
+    gg = torch.load(os.path.join(GOLD, "gauss.pt"), map_location="cpu", weights_only=False)
+    ref = G.GaussianDiffusion(sigmas=R["schedules"].sigma_schedule(
+        "logsnr_cosine_interp", 1000, zero_terminal_snr=True, scale_min=2.0, scale_max=4.0, logsnr_min=-15.0,
+        logsnr_max=15.0), prediction_type="v")
+    real = G.BrownianTreeNoiseSampler
+    G.BrownianTreeNoiseSampler = Recording
+    try:
+        torch.manual_seed(4)
+        a = ref.sample(noise=gg["noise"].clone(), model=lambda x, t=None, y=None, **k: dummy_model(x, t, y=y),
+                       model_kwargs=gg["kw"], guide_scale=9.0, guide_rescale=0.3, solver="dpmpp_2m_sde", steps=12,
+                       t_max=699, t_min=0, discretization="trailing", eta=1.0)
+    finally:
+        G.BrownianTreeNoiseSampler = real
+    assert draws, "the reference's sampler drew no noise"
+    out["gauss_sde"] = dict(out=a, draws=draws)
+
+    rs = R["schedules"]
+    out["schedules"] = [(name, kw, n, rs.beta_schedule(name, n, **kw), rs.sigma_schedule(name, n, **kw))
+                        for name, kw in SCHEDULE_CASES for n in (1000, 50)]
+    torch.save(out, os.path.join(GOLD, "live_reference.pt"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--full", action="store_true")
@@ -785,6 +868,9 @@ def main():
         return
     if args.only == "ddim_branches":
         make_ddim_branches(R)
+        return
+    if args.only == "live_reference":
+        make_live_reference(R)
         return
     if args.only == "vae_full2":
         make_vae_full2(R)

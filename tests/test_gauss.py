@@ -1,5 +1,5 @@
 """GaussianDiffusion / DPM-Solver++(2M) SDE / DDIM inversion: oracle and host
-logic against reference-generated fixtures (tests/golden/gauss.pt) and the live reference."""
+logic against reference-generated fixtures (tests/golden/gauss.pt, live_reference.pt)."""
 import pytest
 import torch
 
@@ -113,25 +113,30 @@ def test_ddimsr_registry_build():
     assert torch.equal(d.reverse_diffusion.sigmas, g["sig_rev"].float())
 
 
-@pytest.mark.reference
 def test_gauss_vs_live_reference_including_sde_noise(emu_backend):
-    """Full stochastic update (eta = 1) with the SAME deterministic Brownian stand-in on both sides."""
-    from oracle import ref_import
-    R = ref_import.load()
-    G = R["diffusion_gauss"]
+    """Full stochastic update (eta = 1) against the reference's sample() with the SAME noise on both sides: every draw of
+    the reference's Brownian sampler, recorded in call order with its interval and the output (tests/golden/
+    live_reference.pt), is replayed to this sampler, which must ask for the same intervals."""
+    r = gold("live_reference.pt")["gauss_sde"]
+    draws = list(r["draws"])
+
+    class Replay:
+        def __init__(self, x, sigma_min, sigma_max, **k):
+            pass
+
+        def __call__(self, sigma, sigma_next):
+            s0, s1, w = draws.pop(0)
+            assert abs(float(sigma) - s0) <= 1e-6 * abs(s0) and abs(float(sigma_next) - s1) <= 1e-6 * abs(s1), (sigma, s0)
+            return w
     fwd, _ = _mine()
-    fwd.noise_sampler_cls = G.BrownianTreeNoiseSampler
-    ref = G.GaussianDiffusion(sigmas=R["schedules"].sigma_schedule(
-        "logsnr_cosine_interp", 1000, zero_terminal_snr=True, scale_min=2.0, scale_max=4.0, logsnr_min=-15.0,
-        logsnr_max=15.0), prediction_type="v")
+    fwd.noise_sampler_cls = Replay
     g = gold("gauss.pt")
     kw = dict(model=_gm, model_kwargs=g["kw"], guide_scale=9.0, guide_rescale=0.3, solver="dpmpp_2m_sde", steps=12,
               t_max=699, t_min=0, discretization="trailing", eta=1.0)
     torch.manual_seed(4)
-    a = ref.sample(noise=g["noise"].clone(), **kw)
-    torch.manual_seed(4)
     b = fwd.sample(noise=g["noise"].clone(), **kw)
-    assert rel_l2(b, a) < 2e-6
+    assert not draws                                    # as many draws as the reference made
+    assert rel_l2(b, r["out"]) < 2e-6
 
 
 # ---- GPU: the three kernels vs the emulator, and the sampler on the device ----------------------------

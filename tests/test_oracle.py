@@ -1,11 +1,11 @@
-"""CPU: the oracle (oracle/torch_ref.py) is pinned (a) against the reference's own modules run
-here (marker `reference`, build container only) and (b) against the committed reference-generated
-fixtures (travels to the GPU box)."""
+"""CPU: the oracle (oracle/torch_ref.py) is pinned (a) against the reference's own modules' outputs on the
+tests' inputs (tests/golden/live_reference.pt) and (b) against the committed reference-generated fixtures of the
+other families — both recorded by oracle/make_golden.py."""
 import pytest
 import torch
 
 from conftest import gold, rel_l2
-from oracle import ref_import, torch_ref
+from oracle import torch_ref
 
 
 # ---- (b) fixtures ---------------------------------------------------------------------------------
@@ -54,66 +54,41 @@ def test_synth_weights_are_nondegenerate_and_reproducible():
 
 
 # ---- (a) live reference ---------------------------------------------------------------------------
-@pytest.mark.reference
 def test_oracle_unet_vs_live_reference():
+    """The tiny UNet on an odd frame count / other resolution / short context, against the reference's own forward
+    recorded on the same seeded weights and inputs (tests/golden/live_reference.pt, oracle/make_golden.py)."""
     from oracle.make_golden import UNET_TINY
-    R = ref_import.load()
-    ref = R["MODEL"].build(dict(type="UNetSD_T2VBase", **UNET_TINY)).eval()
-    sd = torch_ref.synth_state_dict(torch_ref.shapes_of(ref), seed=7)
-    ref.load_state_dict(sd, strict=True)
-    g = torch.Generator().manual_seed(3)
-    x = torch.randn(1, 4, 3, 8, 8, generator=g)        # odd frame count, other resolution
-    y = torch.randn(1, 5, 1024, generator=g)           # short context
-    t = torch.tensor([37])
+    r = gold("live_reference.pt")["unet"]
+    sd = torch_ref.synth_state_dict(r["shapes"], seed=r["seed"])
     with torch.no_grad():
-        assert rel_l2(torch_ref.unet_forward(sd, x, t, y, UNET_TINY["dim"]), ref(x, t, y=y)) < 2e-5
+        assert rel_l2(torch_ref.unet_forward(sd, r["x"], r["t"], r["y"], UNET_TINY["dim"]), r["out"]) < 2e-5
 
 
-@pytest.mark.reference
 def test_oracle_blocks_vs_live_reference():
-    R = ref_import.load()
-    U = R["util"]
-    g = torch.Generator().manual_seed(0)
-
-    def synth(m, seed):
-        sd = torch_ref.synth_state_dict(torch_ref.shapes_of(m), seed=seed)
-        m.load_state_dict(sd, strict=True)
-        return sd
-
+    L = gold("live_reference.pt")
     with torch.no_grad():
-        rb = U.ResBlock(128, 256, 0.1, out_channels=64, use_scale_shift_norm=False).eval()
-        sd = synth(rb, 1)
-        x, e = torch.randn(6, 128, 5, 7, generator=g), torch.randn(6, 256, generator=g)
-        assert rel_l2(torch_ref.resblock({"rb." + k: v for k, v in sd.items()}, "rb", x, e, 2), rb(x, e, 2)) < 2e-5
-        st = U.SpatialTransformer(128, 2, 64, depth=1, context_dim=96, use_linear=True).eval()
-        sd = synth(st, 2)
-        x, c = torch.randn(3, 128, 4, 5, generator=g), torch.randn(3, 9, 96, generator=g)
-        assert rel_l2(torch_ref.spatial_transformer({"m." + k: v for k, v in sd.items()}, "m", x, c), st(x, c)) < 2e-5
-        tt = U.TemporalTransformer(64, 2, 64, depth=1, context_dim=96).eval()      # inner 128 != 64
-        sd = synth(tt, 3)
-        x = torch.randn(2, 64, 6, 3, 4, generator=g)
-        assert rel_l2(torch_ref.temporal_transformer({"m." + k: v for k, v in sd.items()}, "m", x), tt(x)) < 2e-5
+        r = L["resblock"]
+        sd = torch_ref.synth_state_dict(r["shapes"], seed=r["seed"])
+        assert rel_l2(torch_ref.resblock({"rb." + k: v for k, v in sd.items()}, "rb", r["x"], r["e"], 2), r["out"]) < 2e-5
+        r = L["spatial"]
+        sd = torch_ref.synth_state_dict(r["shapes"], seed=r["seed"])
+        assert rel_l2(torch_ref.spatial_transformer({"m." + k: v for k, v in sd.items()}, "m", r["x"], r["c"]), r["out"]) < 2e-5
+        r = L["temporal"]                                                         # inner 128 != 64
+        sd = torch_ref.synth_state_dict(r["shapes"], seed=r["seed"])
+        assert rel_l2(torch_ref.temporal_transformer({"m." + k: v for k, v in sd.items()}, "m", r["x"]), r["out"]) < 2e-5
 
 
-@pytest.mark.reference
 def test_oracle_vae_and_sampler_vs_live_reference():
-    from oracle.make_golden import DDIM_T2V, VAE_TINY, dummy_model
-    R = ref_import.load()
-    vae = R["AUTO_ENCODER"].build(dict(type="AutoencoderKL", ddconfig=VAE_TINY, embed_dim=4)).eval()
-    sd = torch_ref.synth_state_dict(torch_ref.shapes_of(vae), seed=4)
-    vae.load_state_dict(sd, strict=True)
-    g = torch.Generator().manual_seed(1)
+    from oracle.make_golden import dummy_model
+    L = gold("live_reference.pt")
+    r = L["vae"]
+    sd = torch_ref.synth_state_dict(r["shapes"], seed=r["seed"])
     with torch.no_grad():
-        z = torch.randn(1, 4, 6, 10, generator=g)
-        assert rel_l2(torch_ref.vae_decode(sd, z), vae.decode(z)) < 2e-5
-        img = torch.randn(1, 3, 48, 80, generator=g)
-        assert rel_l2(torch_ref.vae_encode_moments(sd, img), vae.encode(img).parameters) < 2e-5
-    diff = R["DIFFUSION"].build(dict(type="DiffusionDDIM", **DDIM_T2V))
-    noise = torch.randn(1, 4, 2, 4, 4, generator=g)
-    kw = [dict(y=torch.randn(1, 3, 8, generator=g)), dict(y=torch.randn(1, 3, 8, generator=g))]
-    a = diff.ddim_sample_loop(noise.clone(), dummy_model, kw, guide_scale=7.5, ddim_timesteps=25, eta=0.0)
-    b = torch_ref.ddim_sample_loop(diff.betas, noise.clone(), dummy_model, kw, 7.5, 25, "v", 0.0)
-    assert torch.equal(a, b)
+        assert rel_l2(torch_ref.vae_decode(sd, r["z"]), r["decode"]) < 2e-5
+        assert rel_l2(torch_ref.vae_encode_moments(sd, r["img"]), r["moments"]) < 2e-5
+    r = L["ddim_loop"]
+    b = torch_ref.ddim_sample_loop(r["betas"], r["noise"].clone(), dummy_model, r["kw"], 7.5, 25, "v", 0.0)
+    assert torch.equal(r["out"], b)
 
 
 # ---------------------------------------------------------------------------------------------------------

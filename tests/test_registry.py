@@ -1,7 +1,5 @@
 """The drop-in seam: yaml `type` strings resolve to the native classes through the reference's
 registry API (utils/registry.py:24-153)."""
-import warnings
-
 import pytest
 
 import vgen_amd
@@ -67,24 +65,30 @@ def test_extra_kwargs_and_unknown_cfg_keys_are_accepted():
     assert mf.precision == "fast" and not mf._asplit and mh.precision == "high"
 
 
-@pytest.mark.reference
-def test_install_overrides_the_reference_registries_in_place():
-    from oracle import ref_import
-    R = ref_import.load()
+def test_install_overrides_the_reference_registries_in_place(monkeypatch):
+    """install() with no argument finds the reference's `utils.registry_class` (MODEL / AUTO_ENCODER / DIFFUSION / EMBEDDER
+    registries, utils/registry_class.py) and re-registers the reference's names IN those registries.  The module is a stand-in
+    here: the registry API restated in vgen_amd.registry, each name first bound to a placeholder class."""
+    import sys
+    import types
+    rc = types.ModuleType("utils.registry_class")
+    for key in ("MODEL", "AUTO_ENCODER", "DIFFUSION", "EMBEDDER"):
+        setattr(rc, key, Registry(key))
     names = (("MODEL", "UNetSD_T2VBase"), ("MODEL", "UNetSD_SR600"), ("MODEL", "UNetSD_I2VGen"), ("MODEL", "UNetSD_VideoLCM"), ("MODEL", "UNetSD_TFT2V"),
              ("AUTO_ENCODER", "AutoencoderKL"), ("DIFFUSION", "DiffusionDDIM"), ("DIFFUSION", "DiffusionDDIMSR"))
-    orig = {(k, n): R[k].get(n) for k, n in names}
-    try:
-        regs = vgen_amd.install()
-        assert regs["MODEL"] is R["MODEL"]
-        assert R["MODEL"].get("UNetSD_T2VBase").__module__ == "vgen_amd.unet"
-        d = R["DIFFUSION"].build(dict(type="DiffusionDDIM", schedule="cosine",
-                                      schedule_param=dict(num_timesteps=1000, cosine_s=0.008,
-                                                          zero_terminal_snr=True), mean_type="v",
-                                      var_type="fixed_small"))
-        assert type(d).__module__ == "vgen_amd.diffusion"
-    finally:
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            for (k, n), cls in orig.items():
-                R[k].register_class(n)(cls)
+    for k, n in names:
+        getattr(rc, k).register_class(n)(type(n, (), {"__module__": "reference"}))
+    utils = types.ModuleType("utils")
+    utils.registry_class = rc
+    monkeypatch.setitem(sys.modules, "utils", utils)
+    monkeypatch.setitem(sys.modules, "utils.registry_class", rc)
+    regs = vgen_amd.install()
+    assert regs["MODEL"] is rc.MODEL and regs["DIFFUSION"] is rc.DIFFUSION and regs["AUTO_ENCODER"] is rc.AUTO_ENCODER
+    for k, n in names:
+        assert getattr(rc, k).get(n).__module__.startswith("vgen_amd."), (k, n)
+    assert rc.MODEL.get("UNetSD_T2VBase").__module__ == "vgen_amd.unet"
+    d = rc.DIFFUSION.build(dict(type="DiffusionDDIM", schedule="cosine",
+                                schedule_param=dict(num_timesteps=1000, cosine_s=0.008,
+                                                    zero_terminal_snr=True), mean_type="v",
+                                var_type="fixed_small"))
+    assert type(d).__module__ == "vgen_amd.diffusion"

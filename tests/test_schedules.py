@@ -1,6 +1,4 @@
-"""Host-side float64 schedule tables: bit-exact vs reference-generated fixtures (and vs the live
-reference where present)."""
-import pytest
+"""Host-side float64 schedule tables: bit-exact vs reference-generated fixtures."""
 import torch
 
 from conftest import gold
@@ -31,14 +29,11 @@ def test_ddim_tables_and_zero_terminal_snr():
     assert abs(float(d.alphas_cumprod[981]) - 7.84e-4) < 1e-5
 
 
-@pytest.mark.reference
 def test_schedules_vs_live_reference():
-    from oracle import ref_import
-    rs = ref_import.load()["schedules"]
-    for name, kw in [("cosine", dict(cosine_s=0.008)), ("cosine", dict(cosine_s=0.008, zero_terminal_snr=True)),
-                     ("linear_sd", dict(init_beta=0.00085, last_beta=0.012)),
-                     ("linear", dict(init_beta=0.0001, last_beta=0.02)),
-                     ("quadratic", dict(init_beta=0.001, last_beta=0.02, zero_terminal_snr=True))]:
-        for n in (1000, 50):
-            assert torch.equal(rs.beta_schedule(name, n, **kw), schedules.beta_schedule(name, n, **kw)), (name, n)
-            assert torch.equal(rs.sigma_schedule(name, n, **kw), schedules.sigma_schedule(name, n, **kw)), (name, n)
+    """Every (schedule, kwargs, n) case of oracle/make_golden.py SCHEDULE_CASES, bit for bit against the reference's own
+    beta_schedule / sigma_schedule outputs (tests/golden/live_reference.pt)."""
+    cases = gold("live_reference.pt")["schedules"]
+    assert len(cases) == 10
+    for name, kw, n, beta, sigma in cases:
+        assert torch.equal(beta, schedules.beta_schedule(name, n, **kw)), (name, n)
+        assert torch.equal(sigma, schedules.sigma_schedule(name, n, **kw)), (name, n)

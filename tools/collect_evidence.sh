@@ -21,7 +21,7 @@ PREC=${PREC:-calibrated}
 CALF=/tmp/vgen_evidence_t2v.cal
 rm -f $CALF
 B="python $R/bench.py --precision $PREC --calibration-file $CALF --no-graph --no-cpu-baseline --no-vae --no-roofline --no-e2e --no-parity --no-scaling-model --variants="
-timeout 900 python $R/bench.py --steps 20 --warmup 5 --dump-shapes --precision $PREC --calibration-file $CALF > $O/bench.json 2> $O/bench.err
+timeout 900 python $R/bench.py --full --steps 20 --warmup 5 --dump-shapes --precision $PREC --calibration-file $CALF > $O/bench.json 2> $O/bench.err
 cp $R/gpurun_out/tapgemm_shapes_t2v_fp16_$PREC.json $R/gpurun_out/other_shapes_t2v_fp16_$PREC.json $O/ 2>/dev/null
 tail -c 1500 $O/bench.json
 if [ -z "${SKIP_PARTITION:-}" ]; then
@@ -39,7 +39,7 @@ for f in ("bench_partition_eager", "bench_partition_eager_rccl", "bench_partitio
 PY
 # the N > 1 launch line of bench.py itself, two ranks sharing the one device over gloo (functional: RCCL refuses two ranks per GPU)
 VGEN_BENCH_ONE_DEVICE=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-  $R/bench.py --gpus 2 --backend gloo --steps 6 --warmup 2 --no-cpu-baseline --no-vae --no-roofline --no-e2e > $O/bench_2ranks_one_device.json 2> $O/bench_2ranks_one_device.err
+  $R/bench.py --full --gpus 2 --backend gloo --steps 6 --warmup 2 --no-cpu-baseline --no-vae --no-roofline --no-e2e > $O/bench_2ranks_one_device.json 2> $O/bench_2ranks_one_device.err
 tail -c 600 $O/bench_2ranks_one_device.json; tail -2 $O/bench_2ranks_one_device.err
 fi
 rm -rf /tmp/prof_kt

@@ -86,10 +86,10 @@ def main():
         from vgen_amd import calibrate as cal
         real_batch = cal.calibration_batch
         cal.calibration_batch = lambda shape, n=None, **k: real_batch(shape, n=4, **dict(k, context=tuple(g["y"].shape[1:])))
-        sys.argv = [sys.argv[0], "--steps", "2", "--warmup", "1", "--no-vae", "--no-cpu-baseline", "--no-parity",
+        sys.argv = [sys.argv[0], "--full", "--steps", "2", "--warmup", "1", "--no-vae", "--no-cpu-baseline", "--no-parity",
                     "--variants", "fp16/mixed,fp16/fast"] + sys.argv[1:]
     else:
-        sys.argv = [sys.argv[0], "--steps", "1", "--warmup", "0", "--no-vae", "--no-cpu-baseline", "--no-scaling-model",
+        sys.argv = [sys.argv[0], "--full", "--steps", "1", "--warmup", "0", "--no-vae", "--no-cpu-baseline", "--no-scaling-model",
                     "--variants", "fp16/mixed"] + sys.argv[1:]
     bench.main()
 
