@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VGEN_ABI_VERSION 5
+#define VGEN_ABI_VERSION 6
 
 enum { VGEN_BF16 = 0, VGEN_F16 = 1, VGEN_F32 = 2 };
 
@@ -234,6 +234,13 @@ typedef struct vgen_attn_args {
 
 int vgen_attention(const vgen_attn_args* args, void* stream);
 
+/* The same operator for head_dim = 80: element (row r, head h, lane e) at ... + r * X_rs + h*80 + e, otherwise the
+ * vgen_attn_args addressing above.  Non-causal only (causal = 1 is rejected), any nq / nk (keys >= nk masked), q/k/v
+ * may be strided views of one fused [rows, 3 * heads * 80] QKV buffer.  Replaces nn.MultiheadAttention inside the
+ * OpenCLIP ViT-H/14 image tower's ResidualAttentionBlocks (16 heads of 80 over 257 tokens), reached through
+ * tools/modules/clip_embedder.py:185 `self.model.encode_image(image)` and :221 `self.model.visual(image)`. */
+int vgen_attention_d80(const vgen_attn_args* args, void* stream);
+
 /* Row softmax: P[r, :] = softmax(S[r, :] * scale), fp32 in -> 16-bit out.
  * Single-head 512-channel VAE attention, autoencoder.py:430-437 (bmm, scale, softmax). */
 int vgen_softmax_rows(const float* S, int64_t rows, int32_t cols, int64_t lds, float scale,
@@ -356,6 +363,16 @@ int vgen_lowfreq_filter(const float* x, int64_t nimg, int32_t H, int32_t W, int3
                         float* y, float* ws, size_t ws_bytes, void* stream);
 /* x[:, c0:c1] *= s in place on rows [M, C] fp32 (unet_sr600.py:278,284: backbone half-channel boost). */
 int vgen_scale_channels(float* x, int64_t M, int32_t C, int32_t c0, int32_t c1, float s, void* stream);
+
+/* Patch embedding of the OpenCLIP image tower as a tap-GEMM A operand (open_clip VisionTransformer.conv1: C -> width,
+ * kernel = stride = P, no bias; reached through tools/modules/clip_embedder.py:185 `self.model.encode_image(image)`).
+ * x fp32 [B, C, H, W] (H % P == W % P == 0); out 16-bit rows [B * (cls + (H/P)*(W/P)), Kpad], row stride Kpad:
+ * row (b, cls + gy*(W/P) + gx) = the patch at (gy, gx) in conv1.weight.reshape(width, C*P*P)'s K order (c, ky, kx),
+ * columns >= C*P*P zero (Kpad % 8 == 0; the tap-GEMM wants Kpad % 64 == 0).  cls = 1 leaves an all-zero row in front
+ * of every image's patches: the CLS slot, which the GEMM's residual (positional_embedding with class_embedding folded
+ * into row 0) fills. */
+int vgen_patchify(const float* x, int64_t B, int32_t C, int32_t H, int32_t W, int32_t P, int32_t Kpad, int32_t cls,
+                  void* out, int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Condition stems ahead of the trunk (prompt constants: evaluated once per sampling session).  fp32, NCHW frames.

@@ -1,0 +1,427 @@
+"""FrozenOpenCLIPTextVisualEmbedder (vgen_amd/clip_visual.py): the embedder every stock config names, with the ViT-H/14 image
+tower on the head_dim-80 attention kernel (vgen_attention_d80) and the patch-embedding stem (vgen_patchify).
+
+Goldens: tests/golden/clip_visual_{tiny,full}.pt, computed by the reference tree's own open_clip 2.16 copy
+(tests/golden/make_clip_golden.py; weights = seeded_state_dict over this embedder's key names, images from a CPU
+generator).  The CPU tests run the host logic on the ABI emulator extended by a test double of the two new entry points
+(oracle/abi_emulator.py's attention is head_dim 64 only)."""
+import ctypes as C
+import json
+import os
+
+import pytest
+import torch
+
+from conftest import GOLD, ROOT, gold, rel_l2
+from oracle.abi_emulator import EmuBackend, _strided
+
+VGEN_E_BADARG = -1
+FAKE = 0x7f0000001000            # aligned, never dereferenced: every call below returns from the argument checks
+
+
+class Emu80(EmuBackend):
+    """The ABI emulator plus the two entry points of ABI 6: attention at head_dim 80 (fp32 softmax of the 16-bit
+    operands, one rounding of the output) and the patchify stem."""
+
+    def attention_d80(self, g):
+        assert not g.causal and g.nbatch % g.inner == 0
+        no, ni = g.nbatch // g.inner, g.inner
+
+        def seqs(t, s, n):
+            rs, bo, bi = s
+            return _strided(t, (no, ni, g.heads, n, 80), (bo, bi, 80, rs, 1)).float()
+
+        q, k, v = seqs(g.q, g.q_s, g.nq), seqs(g.k, g.k_s, g.nk), seqs(g.v, g.v_s, g.nk)
+        rs, bo, bi = g.o_s
+        ov = _strided(g.out, (no, ni, g.heads, g.nq, 80), (bo, bi, 80, rs, 1))
+        ov.copy_((torch.softmax(q @ k.transpose(-1, -2) * g.scale, dim=-1) @ v).to(g.out.dtype))
+        return g.out
+
+    def patchify(self, x, P, Kpad, cls, dt):
+        B, Cin, H, W = x.shape
+        gh, gw = H // P, W // P
+        p = x.reshape(B, Cin, gh, P, gw, P).permute(0, 2, 4, 1, 3, 5).reshape(B, gh * gw, Cin * P * P)
+        out = torch.zeros((B, cls + gh * gw, Kpad), dtype=torch.float32)
+        out[:, cls:, : Cin * P * P] = p
+        return out.reshape(-1, Kpad).to(dt)
+
+
+@pytest.fixture
+def emu80():
+    from vgen_amd import ops
+    prev = ops.set_backend(Emu80())
+    n = torch.get_num_threads()
+    torch.set_num_threads(int(os.environ.get("VGEN_EMU_THREADS", "1")))
+    yield
+    torch.set_num_threads(n)
+    ops.set_backend(prev)
+
+
+def _case(name):
+    from vgen_amd.clip_text import ARCHS
+    from vgen_amd.clip_visual import VISION_ARCHS
+    g = gold(f"clip_visual_{name}.pt")
+    g["text_cfg"] = g["text_cfg"] or ARCHS["ViT-H-14"]
+    g["vision_cfg"] = g["vision_cfg"] or VISION_ARCHS["ViT-H-14"]
+    return g
+
+
+def _images(g, B=None):
+    gen = torch.Generator("cpu").manual_seed(g["image_seed"])
+    S = g["vision_cfg"]["image_size"]
+    return torch.randn((B or g["B"], 3, S, S), generator=gen)
+
+
+def _embedder(g, dtname, sd=None):
+    from vgen_amd.clip_visual import FrozenOpenCLIPTextVisualEmbedder
+    from vgen_amd.synth import seeded_state_dict
+    m = FrozenOpenCLIPTextVisualEmbedder(text_cfg=g["text_cfg"], vision_cfg=g["vision_cfg"], layer=g["layer"],
+                                         compute_dtype=dtname)
+    if sd is None:
+        sd = seeded_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, seed=g["seed"])
+    m.load_state_dict(sd, strict=True)
+    return m
+
+
+# ---- CPU: structure, registry, contract --------------------------------------------------------------------------
+def test_key_set_is_open_clip_vit_h_14():
+    from vgen_amd.clip_visual import FrozenOpenCLIPTextVisualEmbedder
+    with torch.device("meta"):
+        m = FrozenOpenCLIPTextVisualEmbedder()
+    keys = {k: tuple(v.shape) for k, v in m.state_dict().items()}
+    assert len(keys) == 686 and all(k.startswith("model.") for k in keys)
+    n = lambda pred: sum(torch.Size(s).numel() for k, s in keys.items() if pred(k))
+    assert n(lambda k: True) == 986109441
+    assert n(lambda k: k.startswith("model.visual.")) == 632076800
+    assert keys["model.visual.conv1.weight"] == (1280, 3, 14, 14) and keys["model.visual.positional_embedding"] == (257, 1280)
+    assert keys["model.visual.transformer.resblocks.31.attn.in_proj_weight"] == (3840, 1280)
+    assert keys["model.visual.proj"] == (1280, 1024) and keys["model.visual.class_embedding"] == (1280,)
+
+
+def test_stock_configs_build_the_native_embedder():
+    """Every `embedder` dict of the stock configs (tests/golden/clip_embedder_configs.json, `pretrained` dropped) resolves
+    to this class through install()ed registries; the extra keys (vit_resolution, negative_prompt, ...) are accepted."""
+    import vgen_amd
+    from vgen_amd import registry
+    from vgen_amd.clip_visual import FrozenOpenCLIPTextVisualEmbedder
+    cfgs = json.load(open(os.path.join(GOLD, "clip_embedder_configs.json")))
+    assert len(cfgs) == 16
+    reg = {"EMBEDDER": registry.Registry("EMBEDDER")}
+    vgen_amd.install(reg)
+    for name, cfg in cfgs.items():
+        cfg = {k: v for k, v in cfg.items() if k != "pretrained"}
+        with torch.device("meta"):
+            emb = reg["EMBEDDER"].build(cfg)
+        assert type(emb) is FrozenOpenCLIPTextVisualEmbedder, name
+        assert emb.layer_idx == 1 and not any(p.requires_grad for p in emb.parameters()), name
+
+
+def test_string_text_without_open_clip_raises(emu80):
+    try:
+        import open_clip  # noqa: F401
+        pytest.skip("open_clip is installed here")
+    except ImportError:
+        pass
+    g = _case("tiny")
+    m = _embedder(g, "fp16")
+    with pytest.raises(RuntimeError, match="open_clip.tokenize"):
+        m(text=["a cat"])
+
+
+def test_pretrained_checkpoint_loads_strict(tmp_path):
+    """A stock open_clip_pytorch_model.bin has the CLIP keys without the `model.` prefix."""
+    from vgen_amd.clip_visual import FrozenOpenCLIPTextVisualEmbedder
+    g = _case("tiny")
+    m = _embedder(g, "fp16")
+    p = tmp_path / "open_clip_pytorch_model.bin"
+    torch.save({k[len("model."):]: v for k, v in m.state_dict().items()}, p)
+    m2 = FrozenOpenCLIPTextVisualEmbedder(pretrained=str(p), text_cfg=g["text_cfg"], vision_cfg=g["vision_cfg"])
+    assert all(torch.equal(a, b) for a, b in zip(m.state_dict().values(), m2.state_dict().values()))
+    sd = torch.load(p)
+    del sd["visual.proj"]
+    torch.save(sd, p)
+    with pytest.raises(RuntimeError, match="visual.proj"):
+        FrozenOpenCLIPTextVisualEmbedder(pretrained=str(p), text_cfg=g["text_cfg"], vision_cfg=g["vision_cfg"])
+
+
+def _good_attn():
+    from vgen_amd import lib
+    a = lib.AttnArgs()
+    a.q = a.k = a.v = a.out = FAKE
+    a.dtype, a.heads, a.nq, a.nk, a.nbatch, a.inner = lib.VGEN_F16, 16, 257, 257, 2, 1
+    a.q_rs = a.k_rs = a.v_rs = 3840
+    a.q_bo = a.k_bo = a.v_bo = 257 * 3840
+    a.o_rs, a.o_bo = 1280, 257 * 1280
+    a.scale = 80 ** -0.5
+    return a
+
+
+ATTN_BAD = [
+    ("dtype", lambda a: setattr(a, "dtype", 2), b"dtype"),
+    ("heads", lambda a: setattr(a, "heads", 0), b"sizes"),
+    ("nq", lambda a: setattr(a, "nq", 0), b"sizes"),
+    ("nk", lambda a: setattr(a, "nk", -1), b"sizes"),
+    ("inner", lambda a: setattr(a, "inner", 3), b"sizes"),
+    ("null", lambda a: setattr(a, "v", None), b"null"),
+    ("align", lambda a: setattr(a, "k", FAKE + 8), b"alignment"),
+    ("stride", lambda a: setattr(a, "q_rs", 3844), b"multiples of 8"),
+    ("causal", lambda a: setattr(a, "causal", 1), b"causal"),
+]
+
+
+@pytest.mark.parametrize("name,mutate,needle", ATTN_BAD, ids=[b[0] for b in ATTN_BAD])
+def test_attention_d80_rejects_before_launching(name, mutate, needle):
+    from vgen_amd import lib
+    l = lib.load()
+    a = _good_attn()
+    mutate(a)
+    assert l.vgen_attention_d80(C.byref(a), None) == VGEN_E_BADARG
+    assert needle in l.vgen_last_error(), (name, l.vgen_last_error())
+
+
+def test_attention_d80_null_args():
+    from vgen_amd import lib
+    l = lib.load()
+    assert l.vgen_attention_d80(None, None) == VGEN_E_BADARG and b"null" in l.vgen_last_error()
+
+
+PATCH_GOOD = dict(x=FAKE, B=2, C=3, H=224, W=224, P=14, Kpad=640, cls=1, out=FAKE, dtype=1)
+PATCH_BAD = [
+    ("null", dict(x=None), b"null"),
+    ("dtype", dict(dtype=2), b"dtype"),
+    ("B", dict(B=0), b"patches"),
+    ("ragged", dict(H=230), b"patches"),
+    ("cls", dict(cls=2), b"cls"),
+    ("Kpad_short", dict(Kpad=584), b"Kpad"),
+    ("Kpad_align", dict(Kpad=644), b"Kpad"),
+    ("out_align", dict(out=FAKE + 4), b"alignment"),
+]
+
+
+@pytest.mark.parametrize("name,change,needle", PATCH_BAD, ids=[b[0] for b in PATCH_BAD])
+def test_patchify_rejects_before_launching(name, change, needle):
+    from vgen_amd import lib
+    l = lib.load()
+    a = dict(PATCH_GOOD, **change)
+    rc = l.vgen_patchify(a["x"], a["B"], a["C"], a["H"], a["W"], a["P"], a["Kpad"], a["cls"], a["out"], a["dtype"], None)
+    assert rc == VGEN_E_BADARG
+    assert needle in l.vgen_last_error(), (name, l.vgen_last_error())
+
+
+def test_d80_kernel_compiles_without_spills(tmp_path):
+    """flash_d80_kernel lives in attention.hip, which tests/test_abi.py's spill guard compiles as a whole; this pins the
+    new instantiations by name (zero VGPR / SGPR spills, no scratch) so that a later edit cannot lose them unnoticed."""
+    import re
+    import subprocess
+    from vgen_amd import build as b
+    for src, kname in (("attention.hip", "flash_d80_kernel"), ("stems.hip", "patchify_kernel")):
+        out = tmp_path / (src + ".s")
+        flags = [f for f in b.FLAGS if f != "-fPIC"]
+        r = subprocess.run([b._hipcc()] + flags + ["-S", "--cuda-device-only", os.path.join(b.CSRC, src), "-o", str(out)],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        txt = out.read_text()
+        metas = [m for m in re.split(r"\n\s+- \.agpr_count:", txt) if kname in m.split(".name:")[-1][:200]]
+        assert len(metas) == 2, kname                          # bf16 + fp16
+        for m in metas:
+            assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", m).group(1)) == 0, kname
+            assert int(re.search(r"\.sgpr_spill_count:\s+(\d+)", m).group(1)) == 0, kname
+            assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", m).group(1)) == 0, kname
+
+
+@pytest.mark.reference
+def test_key_set_equals_the_reference_open_clip():
+    """Our key names and shapes are exactly the fork's CLIP.state_dict() for ViT-H-14 (tests/golden/make_clip_golden.py
+    loads the reference tree's own open_clip copy).  In a child process: importing that copy imports `transformers`
+    under a stub torchvision, and `transformers` caches what it found."""
+    import subprocess
+    import sys
+    from vgen_amd.clip_visual import FrozenOpenCLIPTextVisualEmbedder
+    code = ("import json, sys, torch; sys.path.insert(0, %r); sys.path.insert(0, %r); import make_clip_golden as mk; "
+            "from oracle.ref_import import REF; from vgen_amd.clip_text import ARCHS; "
+            "from vgen_amd.clip_visual import VISION_ARCHS\n"
+            "with torch.device('meta'): m = mk.fork_clip(mk.load_fork(REF), ARCHS['ViT-H-14'], VISION_ARCHS['ViT-H-14'])\n"
+            "print(json.dumps({k: list(v.shape) for k, v in m.state_dict().items()}))") % (ROOT, GOLD)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    fork = {k: tuple(v) for k, v in json.loads(r.stdout.strip().splitlines()[-1]).items()}
+    with torch.device("meta"):
+        ours = {k[len("model."):]: tuple(v.shape) for k, v in FrozenOpenCLIPTextVisualEmbedder().state_dict().items()}
+    assert ours == fork
+
+
+# ---- CPU: host logic on the emulator --------------------------------------------------------------------------------
+def test_tiny_embedder_on_emulator_vs_open_clip_golden(emu80):
+    g = _case("tiny")
+    m = _embedder(g, "fp16")
+    xi, xt, x = m(image=_images(g), text=g["tokens"])
+    assert xi.shape == g["xi"].shape and xt.shape == g["xt"].shape and x.shape == g["x"].shape
+    assert rel_l2(xi, g["xi"]) < 2e-3 and rel_l2(xt, g["xt"]) < 3e-3 and rel_l2(x, g["x"]) < 3e-3
+    assert m(text=g["tokens"])[0] is None
+    with pytest.raises(ValueError, match="224"):
+        m.encode_image(torch.zeros(1, 3, 112, 112))
+
+
+def test_engine_sequence_registry_model_to_forward(emu80):
+    """What an engine does (inference_i2vgen_entrance.py:136-138, 188): EMBEDDER.build(cfg.embedder), then
+    `clip_encoder.model.to(gpu)` on the INNER module, then forward — the packed operands follow the parameters (here: a
+    dtype move of the inner module and an in-place reload, both invisible to the wrapper)."""
+    import vgen_amd
+    from vgen_amd import registry
+    g = _case("tiny")
+    reg = {"EMBEDDER": registry.Registry("EMBEDDER")}
+    vgen_amd.install(reg)
+    emb = reg["EMBEDDER"].build(dict(type="FrozenOpenCLIPTextVisualEmbedder", layer="penultimate", vit_resolution=[224, 224],
+                                     text_cfg=g["text_cfg"], vision_cfg=g["vision_cfg"], compute_dtype="fp16"))
+    ref = _embedder(g, "fp16")
+    sd = ref.state_dict()
+    emb.load_state_dict(sd, strict=True)
+    img = _images(g)
+    xi0 = emb.encode_image(img)                               # packs
+    emb.model.to(torch.float64)                               # the inner module moves: new storage
+    emb.model.to(torch.float32)
+    xi1, xt1, x1 = emb(image=img, text=g["tokens"])
+    assert torch.equal(xi0, xi1) and rel_l2(xi1, g["xi"]) < 2e-3 and rel_l2(xt1, g["xt"]) < 3e-3
+    with torch.no_grad():                                     # in-place change of a weight the wrapper already packed
+        emb.model.visual.proj.mul_(2.0)
+    assert rel_l2(emb.encode_image(img), 2 * xi1) < 1e-6
+
+
+def test_full_size_fp16_error_predicted_on_emulator(emu80):
+    """The full ViT-H-14 embedder on the emulator (16-bit GEMM operands, P and the GELU output rounded as the kernels do)
+    against the open_clip golden: the CPU prediction of the GPU's fp16 error, before any GPU run."""
+    g = _case("full")
+    m = _embedder(g, "fp16")
+    torch.set_num_threads(min(8, os.cpu_count() or 1))
+    xi, xt, x = m(image=_images(g), text=g["tokens"])
+    errs = {"xi": rel_l2(xi, g["xi"]), "xt": rel_l2(xt, g["xt"]), "x": rel_l2(x, g["x"])}
+    print("emulator fp16 vs open_clip golden:", errs)
+    assert errs["xi"] < 2e-3 and errs["xt"] < 2.5e-3 and errs["x"] < 2.5e-3, errs
+
+
+# ---- GPU ----------------------------------------------------------------------------------------------------------
+DEV = "cuda:0"
+
+
+def _attn_ref(q, k, v, scale):
+    return torch.softmax(q.double() @ k.double().transpose(-1, -2) * scale, dim=-1) @ v.double()
+
+
+def _run_d80(be, dt, B, heads, nq, nk, fused, seed):
+    from vgen_amd.ops import Attn
+    g = torch.Generator("cpu").manual_seed(seed)
+    d = heads * 80
+    if fused:                                 # q/k/v as strided views of one [rows, 3 d] QKV buffer (the towers' layout)
+        assert nq == nk
+        qkv = (torch.randn((B * nq, 3 * d), generator=g) * 1.5).to(dt).to(DEV)
+        q, k, v = qkv, qkv[:, d:], qkv[:, 2 * d:]
+        ld = 3 * d
+        qs = ks = vs = (ld, nq * ld, 0)
+        qh = qkv.view(B, nq, 3, heads, 80).permute(2, 0, 3, 1, 4).float().cpu()
+        Q, K, V = qh[0], qh[1], qh[2]
+    else:
+        q = (torch.randn((B * nq, d), generator=g) * 1.5).to(dt).to(DEV)
+        k = (torch.randn((B * nk, d), generator=g) * 1.5).to(dt).to(DEV)
+        v = torch.randn((B * nk, d), generator=g).to(dt).to(DEV)
+        qs, ks, vs = (d, nq * d, 0), (d, nk * d, 0), (d, nk * d, 0)
+        Q = q.view(B, nq, heads, 80).permute(0, 2, 1, 3).float().cpu()
+        K = k.view(B, nk, heads, 80).permute(0, 2, 1, 3).float().cpu()
+        V = v.view(B, nk, heads, 80).permute(0, 2, 1, 3).float().cpu()
+    outs = []
+    for _ in range(2):
+        o = torch.full((B * nq, d), float("nan"), dtype=dt, device=DEV)
+        be.attention_d80(Attn(q=q, k=k, v=v, out=o, heads=heads, nq=nq, nk=nk, nbatch=B, inner=1, q_s=qs, k_s=ks, v_s=vs,
+                              o_s=(d, nq * d, 0), scale=80 ** -0.5))
+        torch.cuda.synchronize()
+        outs.append(o.cpu())
+    ref = _attn_ref(Q, K, V, 80 ** -0.5).permute(0, 2, 1, 3).reshape(B * nq, d)
+    return outs, ref
+
+
+D80_CASES = {
+    "257x257_b1": dict(B=1, heads=16, nq=257, nk=257, fused=False),
+    "257x257_b5": dict(B=5, heads=16, nq=257, nk=257, fused=False),
+    "fused_qkv_257": dict(B=3, heads=16, nq=257, nk=257, fused=True),
+    "nk77": dict(B=2, heads=4, nq=200, nk=77, fused=False),
+    "nk130": dict(B=2, heads=4, nq=130, nk=130, fused=True),
+    "nq20": dict(B=3, heads=4, nq=20, nk=300, fused=False),
+    "nq1": dict(B=2, heads=2, nq=1, nk=257, fused=False),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtname", ["fp16", "bf16"])
+@pytest.mark.parametrize("name", list(D80_CASES))
+def test_attention_d80_on_device(hip_backend, dtname, name):
+    """vgen_attention_d80 against fp64 attention of the same 16-bit operands at the d64 bound (3 x TOL16: P is rounded to
+    16 bit before the PV product); an error per output column (a misaligned transpose read of V corrupts whole columns);
+    two launches bit-identical."""
+    import kernel_cases as kc
+    dt = {"fp16": torch.float16, "bf16": torch.bfloat16}[dtname]
+    outs, ref = _run_d80(hip_backend, dt, seed=7, **D80_CASES[name])
+    o = outs[0].double()
+    assert torch.isfinite(o).all()
+    err = float((o - ref).norm() / ref.norm())
+    assert err <= 3 * kc.TOL16[dtname], err
+    col = ((o - ref).norm(dim=0) / ref.norm(dim=0).clamp_min(1e-30)).view(-1, 80).max(0).values
+    assert float(col.max()) <= 6 * kc.TOL16[dtname], col
+    assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16))
+
+
+@pytest.mark.gpu
+def test_patchify_on_device(hip_backend):
+    g = torch.Generator("cpu").manual_seed(3)
+    x = torch.randn((3, 3, 224, 224), generator=g)
+    got = hip_backend.patchify(x.to(DEV), 14, 640, 1, torch.float16).cpu()
+    want = Emu80().patchify(x, 14, 640, 1, torch.float16)
+    assert torch.equal(got.view(torch.int16), want.view(torch.int16))
+
+
+def _parity(key, err):
+    """Measured error into the suite's parity record, next to the text tower's and the UNet's (test_gpu_model._record)."""
+    from test_gpu_model import _record
+    _record(key, err)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtname,tol", [("fp16", 2e-3), ("bf16", 2e-2)])
+def test_tiny_embedder_on_device(hip_backend, dtname, tol):
+    g = _case("tiny")
+    m = _embedder(g, dtname)
+    m.model.to(DEV)                                           # the engines' move of the inner module
+    xi, xt, x = m(image=_images(g), text=g["tokens"].to(DEV))
+    assert xi.is_cuda and x.shape == g["x"].shape
+    errs = {"xi": rel_l2(xi, g["xi"]), "xt": rel_l2(xt, g["xt"]), "x": rel_l2(x, g["x"])}
+    assert all(e < tol for e in errs.values()), errs
+
+
+@pytest.fixture(scope="module")
+def full_sd():
+    from vgen_amd.synth import seeded_state_dict
+    from vgen_amd.clip_visual import FrozenOpenCLIPTextVisualEmbedder
+    g = _case("full")
+    with torch.device("meta"):
+        shapes = {k: tuple(v.shape) for k, v in FrozenOpenCLIPTextVisualEmbedder().state_dict().items()}
+    return seeded_state_dict(shapes, seed=g["seed"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtname,tol_i,tol_t", [("fp16", 2e-3, 2.5e-3), ("bf16", 2e-2, 2e-2)])
+def test_full_vit_h_14_on_device(hip_backend, full_sd, dtname, tol_i, tol_t):
+    """Full ViT-H-14 (986 M parameters) against the reference's open_clip; a batch of 3 (golden images + a third) meets
+    the same image bound on its first two rows (the tap-GEMM plan may change with M: not a bitwise check)."""
+    from vgen_amd.clip_visual import FrozenOpenCLIPTextVisualEmbedder
+    g = _case("full")
+    with torch.device("meta"):
+        m = FrozenOpenCLIPTextVisualEmbedder(layer=g["layer"], compute_dtype=dtname)
+    m.load_state_dict(full_sd, strict=True, assign=True)
+    m.model.to(DEV)
+    img = _images(g, B=3)
+    xi, xt, x = m(image=img[:2].to(DEV), text=g["tokens"].to(DEV))
+    errs = {"xi": rel_l2(xi, g["xi"]), "xt": rel_l2(xt, g["xt"]), "x": rel_l2(x, g["x"])}
+    xi3 = m.encode_image(img.to(DEV))
+    errs["xi_b3"] = rel_l2(xi3[:2], g["xi"])
+    for k, e in errs.items():
+        _parity(f"clip_visual_vit_h/{dtname}/{k}", e)
+    assert xi.shape == (2, 1024) and xt.shape == (2, 1024) and x.shape == (2, 77, 1024)
+    assert errs["xi"] <= tol_i and errs["xi_b3"] <= tol_i and errs["xt"] <= tol_t and errs["x"] <= tol_t, errs

@@ -32,6 +32,44 @@ from .ops import Attn, TapGemm
 HEAD_DIM = 64
 
 
+def pack_blocks(resblocks, dt):
+    """Kernel operands of open_clip ResidualAttentionBlocks: fp32 LayerNorm parameters and biases, 16-bit weights."""
+    f32 = lambda t: t.detach().float().contiguous()
+    w16 = lambda t: t.detach().to(dt).contiguous()
+    return [dict(ln1=(f32(b.ln_1.weight), f32(b.ln_1.bias)), ln2=(f32(b.ln_2.weight), f32(b.ln_2.bias)),
+                 qkv=(w16(b.attn.in_proj_weight), f32(b.attn.in_proj_bias)),          # rows q | k | v
+                 o=(w16(b.attn.out_proj.weight), f32(b.attn.out_proj.bias)),
+                 fc=(w16(b.mlp.c_fc.weight), f32(b.mlp.c_fc.bias)),
+                 pr=(w16(b.mlp.c_proj.weight), f32(b.mlp.c_proj.bias))) for b in resblocks]
+
+
+def residual_blocks(be, x, blocks, B, L, heads, head_dim, causal, dt):
+    """open_clip ResidualAttentionBlocks over the fp32 residual stream x [B*L, heads*head_dim] (both CLIP towers):
+
+        x = x + out_proj(MHA(ln_1(x)))            fused QKV tap-GEMM, flash attention (head_dim 64 or 80), residual epilogue
+        x = x + c_proj(gelu(c_fc(ln_2(x))))       exact-GELU cast pass between the two tap-GEMMs
+
+    Text tower: head_dim 64, causal (clip_embedder.py:157 attn_mask); image tower: head_dim 80, no mask."""
+    M, d = B * L, heads * head_dim
+    attention = {64: be.attention, 80: getattr(be, "attention_d80", None)}.get(head_dim)
+    if attention is None:
+        raise NotImplementedError(f"no attention kernel for head_dim {head_dim} (64 and 80 are built)")
+    ld = 3 * d
+    for blk in blocks:
+        n = be.layernorm(x, *blk["ln1"], 1e-5, dt)
+        qkv = be.tapgemm(TapGemm(A=n, W=blk["qkv"][0], M=M, N=3 * d, C1=d, bias=blk["qkv"][1], out_dtype=dt))
+        o = torch.empty((M, d), dtype=dt, device=x.device)
+        attention(Attn(q=qkv, k=qkv[:, d:], v=qkv[:, 2 * d:], out=o, heads=heads, nq=L, nk=L, nbatch=B, inner=1,
+                       q_s=(ld, L * ld, 0), k_s=(ld, L * ld, 0), v_s=(ld, L * ld, 0), o_s=(d, L * d, 0),
+                       scale=head_dim ** -0.5, causal=causal))
+        x = be.tapgemm(TapGemm(A=o, W=blk["o"][0], M=M, N=d, C1=d, bias=blk["o"][1], residual=x))
+        n = be.layernorm(x, *blk["ln2"], 1e-5, dt)
+        h = be.tapgemm(TapGemm(A=n, W=blk["fc"][0], M=M, N=blk["fc"][0].shape[0], C1=d, bias=blk["fc"][1]))
+        h = be.act_cast(h, 2, dt)                                         # nn.GELU, exact (erf) form
+        x = be.tapgemm(TapGemm(A=h, W=blk["pr"][0], M=M, N=d, C1=h.shape[1], bias=blk["pr"][1], residual=x))
+    return x
+
+
 class _MLPP(nn.Module):
     def __init__(self, d, hidden):
         super().__init__()
@@ -120,18 +158,10 @@ class FrozenOpenCLIPEmbedder(nn.Module):
     def pack(self):
         dt = self.compute_dtype
         f32 = lambda t: t.detach().float().contiguous()
-        w16 = lambda t: t.detach().to(dt).contiguous()
         m = self.model
         P = {"tok": f32(m.token_embedding.weight), "pos": f32(m.positional_embedding),
              "lnf": (f32(m.ln_final.weight), f32(m.ln_final.bias)),
-             "proj": f32(m.text_projection.t()), "blocks": []}
-        for b in m.transformer.resblocks:
-            P["blocks"].append(dict(
-                ln1=(f32(b.ln_1.weight), f32(b.ln_1.bias)), ln2=(f32(b.ln_2.weight), f32(b.ln_2.bias)),
-                qkv=(w16(b.attn.in_proj_weight), f32(b.attn.in_proj_bias)),          # rows q | k | v
-                o=(w16(b.attn.out_proj.weight), f32(b.attn.out_proj.bias)),
-                fc=(w16(b.mlp.c_fc.weight), f32(b.mlp.c_fc.bias)),
-                pr=(w16(b.mlp.c_proj.weight), f32(b.mlp.c_proj.bias))))
+             "proj": f32(m.text_projection.t()), "blocks": pack_blocks(m.transformer.resblocks, dt)}
         self._packed = P
         return P
 
@@ -144,24 +174,11 @@ class FrozenOpenCLIPEmbedder(nn.Module):
             self.pack()
         P = self._packed
         B, Lk = tokens.shape
-        d, heads = self.cfg["width"], self.cfg["heads"]
+        heads = self.cfg["heads"]
         assert Lk == P["pos"].shape[0], "context length is fixed by positional_embedding"
-        M = B * Lk
         x = be.embed_tokens(tokens.to(P["tok"].device).long().contiguous(), P["tok"], P["pos"])
         nblocks = len(P["blocks"]) - self.layer_idx                      # text_transformer_forward: :55-64
-        for blk in P["blocks"][:nblocks]:
-            n = be.layernorm(x, *blk["ln1"], 1e-5, dt)
-            qkv = be.tapgemm(TapGemm(A=n, W=blk["qkv"][0], M=M, N=3 * d, C1=d, bias=blk["qkv"][1], out_dtype=dt))
-            o = torch.empty((M, d), dtype=dt, device=x.device)
-            ld = 3 * d
-            be.attention(Attn(q=qkv, k=qkv[:, d:], v=qkv[:, 2 * d:], out=o, heads=heads, nq=Lk, nk=Lk, nbatch=B, inner=1,
-                              q_s=(ld, Lk * ld, 0), k_s=(ld, Lk * ld, 0), v_s=(ld, Lk * ld, 0), o_s=(d, Lk * d, 0),
-                              scale=HEAD_DIM ** -0.5, causal=True))
-            x = be.tapgemm(TapGemm(A=o, W=blk["o"][0], M=M, N=d, C1=d, bias=blk["o"][1], residual=x))
-            n = be.layernorm(x, *blk["ln2"], 1e-5, dt)
-            h = be.tapgemm(TapGemm(A=n, W=blk["fc"][0], M=M, N=blk["fc"][0].shape[0], C1=d, bias=blk["fc"][1]))
-            h = be.act_cast(h, 2, dt)                                         # nn.GELU, exact (erf) form
-            x = be.tapgemm(TapGemm(A=h, W=blk["pr"][0], M=M, N=d, C1=h.shape[1], bias=blk["pr"][1], residual=x))
+        x = residual_blocks(be, x, P["blocks"][:nblocks], B, Lk, heads, HEAD_DIM, True, dt)
         return be.layernorm(x, *P["lnf"], 1e-5, torch.float32)
 
     @torch.no_grad()

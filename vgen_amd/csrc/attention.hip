@@ -1,6 +1,7 @@
-// attention.hip — fused softmax(Q K^T * scale) V for head_dim 64 on gfx950 MFMA.
+// attention.hip — fused softmax(Q K^T * scale) V for head_dim 64 (and 80) on gfx950 MFMA.
 //
-// Two kernels (see include/vgen_hip.h for the strided sequence addressing):
+// Two head_dim-64 kernels (see include/vgen_hip.h for the strided sequence addressing), plus flash_d80_kernel, the
+// head_dim-80 variant of flash_kernel for the CLIP image tower (described where it is defined):
 //
 //  flash_kernel    : general nq x nk (spatial self-attention 1792/448/112/28 tokens, cross
 //                    attention over 77 context tokens).  Block = 4 waves x 32 queries, KV tiles
@@ -278,6 +279,221 @@ __global__ __launch_bounds__(256, 2) void flash_kernel(const vgen_attn_args p, i
 
 
 // =========================================================================================
+// head_dim 80: the OpenCLIP ViT-H/14 image tower (16 heads of 80 over 257 tokens, tools/modules/clip_embedder.py:221
+// `self.model.visual(image)`).  Same structure as flash_kernel (transposed products, one query column per lane, online
+// softmax in fp32, double-buffered K / V tiles of 64 keys, 4 waves x 32 queries), with three differences:
+//   - S^T = K Q^T contracts 80 = 32 + 32 + 16 as three 16x16x32 MFMAs; in the third, the Q fragment of lanes 32..63
+//     (d 80..95) is zero, so their K fragment (a duplicate of d 64..79, never padding) contributes nothing.  A 16x16x16
+//     MFMA for the tail, accumulating onto the 16x16x32 chain's result, was tried first: the compiled code issued it
+//     without wait states right behind the 16x16x32 that writes its SrcC, and it read the stale register (wrong rows
+//     in the second query fragment, measured on the GPU) — one opcode per accumulator chain avoids that hazard;
+//   - O^T = V^T P^T has five 16-row d tiles;
+//   - K and V are both staged row-major with row stride 80 elements (160 B, no pad, no swizzle).  For the transpose
+//     reads of V the 8 rows x 32 B a half-wave touches sit at word offsets 0, 40, 16, 56, 32, 8, 48, 24 (+ 8 per d tile):
+//     all 64 banks once, and every address is a multiple of 8 B (160 B rows, 32 B d tiles, 8 B per (lr & 3) step).
+//     The K fragment reads (16 B per lane, 8 rows per quarter-wave) land on the same word offsets + 4 lq: disjoint too.
+// Non-causal only (the image tower has no mask); the entry point rejects causal = 1.
+template <typename T>
+__global__ __launch_bounds__(256, 2) void flash_d80_kernel(const vgen_attn_args p, int qtiles) {
+  constexpr int D = 80, BQ = 128, BKV = 64, RS = 80;   // RS: LDS row stride (elements) of K and V
+  constexpr int CH = BKV * D / 8;                      // 16-B chunks per tile: 640 = 2.5 per thread
+  __shared__ __attribute__((aligned(16))) uint16_t sK[2][BKV * RS];
+  __shared__ __attribute__((aligned(16))) uint16_t sV[2][BKV * RS];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lr = lane & 15, lq = lane >> 4;
+
+  int64_t bid = blockIdx.x;
+  const int qt = (int)(bid % qtiles);
+  bid /= qtiles;
+  const int h = (int)(bid % p.heads);
+  const int64_t bi = bid / p.heads;
+
+  const uint16_t* Q = (const uint16_t*)p.q + seq_off(bi, p.inner, p.q_bo, p.q_bi) + h * D;
+  const uint16_t* K = (const uint16_t*)p.k + seq_off(bi, p.inner, p.k_bo, p.k_bi) + h * D;
+  const uint16_t* V = (const uint16_t*)p.v + seq_off(bi, p.inner, p.v_bo, p.v_bi) + h * D;
+  uint16_t* O = (uint16_t*)p.out + seq_off(bi, p.inner, p.o_bo, p.o_bi) + h * D;
+
+  const int q0 = qt * BQ + wave * 32;
+  // a wave whose 32 queries all lie past nq (the last query tile of 257 tokens holds one) stages K / V for the block
+  // but skips the products (wave-uniform)
+  const bool active = q0 < p.nq;
+
+  // Q fragments (B operand): lane (lq, lr): Q[q0 + 16 f + lr][32 ks + 8 lq .. +8], ks = 0, 1, 2; d >= 80 (lq >= 2 at
+  // ks = 2) is zero
+  u32x4 qf[2][3];
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const int row = q0 + f * 16 + lr;
+    const uint16_t* src = Q + (int64_t)row * p.q_rs;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) qf[f][ks] = row < p.nq ? *(const u32x4*)(src + ks * 32 + lq * 8) : u32x4{0u, 0u, 0u, 0u};
+    qf[f][2] = row < p.nq && lq < 2 ? *(const u32x4*)(src + 64 + lq * 8) : u32x4{0u, 0u, 0u, 0u};
+  }
+
+  f32x4 o_acc[2][5];
+  float m_run[2], l_run[2];
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    m_run[f] = -INFINITY;
+    l_run[f] = 0.f;
+#pragma unroll
+    for (int d = 0; d < 5; ++d) o_acc[f][d] = f32x4{0, 0, 0, 0};
+  }
+  const float c = p.scale * 1.44269504088896340736f;  // scores -> log2 domain
+
+  // staging: chunk j = tid + 256 i (i < 3, j < 640) -> key j / 10, elements 8 (j % 10) .. + 8, for K and V alike
+  u32x4 rk[3], rv[3];
+  auto gload = [&](int kv0) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int j = tid + 256 * i, key = j / 10, col = (j % 10) * 8;
+      rk[i] = rv[i] = u32x4{0u, 0u, 0u, 0u};
+      if (j < CH && kv0 + key < p.nk) {
+        rk[i] = *(const u32x4*)(K + (int64_t)(kv0 + key) * p.k_rs + col);
+        rv[i] = *(const u32x4*)(V + (int64_t)(kv0 + key) * p.v_rs + col);
+      }
+    }
+  };
+  auto lstore = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int j = tid + 256 * i, key = j / 10, col = (j % 10) * 8;
+      if (j < CH) {
+        *(u32x4*)(sK[buf] + key * RS + col) = rk[i];
+        *(u32x4*)(sV[buf] + key * RS + col) = rv[i];
+      }
+    }
+  };
+
+  const int ntile = (p.nk + BKV - 1) / BKV;
+  gload(0);
+  lstore(0);
+  __syncthreads();
+  for (int t = 0; t < ntile; ++t) {
+    const int kv0 = t * BKV;
+    const int buf = t & 1;
+    const bool more = t + 1 < ntile;
+    if (more) gload(kv0 + BKV);
+    const uint16_t* cK = sK[buf];
+    const uint16_t* cV = sV[buf];
+
+    if (active) {
+      // ---- S^T = K Q^T: three 16x16x32 steps over d 0..31, 32..63, 64..79 (+ 16 zero columns of Q) ---------
+      f32x4 s[2][4];
+#pragma unroll
+      for (int kf = 0; kf < 4; ++kf) {
+        const uint16_t* kr = cK + (kf * 16 + lr) * RS;
+        const u32x4 k0 = *(const u32x4*)(kr + lq * 8);
+        const u32x4 k1 = *(const u32x4*)(kr + 32 + lq * 8);
+        const u32x4 k2 = *(const u32x4*)(kr + 64 + (lq & 1) * 8);     // lanes 32..63: d 64..79 again (times zero)
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          f32x4 a = T::mfma32(k0, qf[f][0], f32x4{0, 0, 0, 0});
+          a = T::mfma32(k1, qf[f][1], a);
+          s[f][kf] = T::mfma32(k2, qf[f][2], a);
+        }
+      }
+
+      // ---- online softmax; lane (lq, lr) holds keys kv0 + 16 kf + 4 lq + r of query lr ----------------------
+      const bool ragged = kv0 + BKV > p.nk;
+      u32x4 pb[2][2];
+#pragma unroll
+      for (int f = 0; f < 2; ++f) {
+        if (ragged) {   // block-uniform: only the last KV tile pays for the key mask
+#pragma unroll
+          for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              s[f][kf][r] = (kv0 + kf * 16 + lq * 4 + r < p.nk) ? s[f][kf][r] : -INFINITY;
+        }
+        float mx = fmaxf(s[f][0][0], s[f][0][1]);
+#pragma unroll
+        for (int kf = 0; kf < 4; ++kf) {
+          if (kf > 0) mx = __builtin_fmaxf(__builtin_fmaxf(mx, s[f][kf][0]), s[f][kf][1]);
+          mx = __builtin_fmaxf(__builtin_fmaxf(mx, s[f][kf][2]), s[f][kf][3]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run[f], mx);  // finite: every tile has >= 1 valid key
+        const bool grew = __builtin_amdgcn_ballot_w64(m_new > m_run[f]) != 0ull;
+        const float mc = m_new * c;
+        float pv[4][4];
+        const f32x2 c2 = {c, c}, mc2 = {mc, mc};
+        f32x2 ps2 = {0.f, 0.f};
+#pragma unroll
+        for (int kf = 0; kf < 4; ++kf) {
+          const f32x2 a = f32x2{s[f][kf][0], s[f][kf][1]} * c2 - mc2;
+          const f32x2 b = f32x2{s[f][kf][2], s[f][kf][3]} * c2 - mc2;
+          const f32x2 ea = {fast_exp2(a.x), fast_exp2(a.y)};
+          const f32x2 eb = {fast_exp2(b.x), fast_exp2(b.y)};
+          pv[kf][0] = ea.x;
+          pv[kf][1] = ea.y;
+          pv[kf][2] = eb.x;
+          pv[kf][3] = eb.y;
+          ps2 += ea;
+          ps2 += eb;
+        }
+        const float psum = ps2.x + ps2.y;
+        if (grew) {
+          const float alpha = fast_exp2((m_run[f] - m_new) * c);
+          m_run[f] = m_new;
+          l_run[f] = l_run[f] * alpha + psum;
+#pragma unroll
+          for (int d = 0; d < 5; ++d) o_acc[f][d] *= alpha;
+        } else {
+          l_run[f] += psum;
+        }
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+          u32x4 tt;
+          tt.x = pack2<T>(pv[2 * st][0], pv[2 * st][1]);
+          tt.y = pack2<T>(pv[2 * st][2], pv[2 * st][3]);
+          tt.z = pack2<T>(pv[2 * st + 1][0], pv[2 * st + 1][1]);
+          tt.w = pack2<T>(pv[2 * st + 1][2], pv[2 * st + 1][3]);
+          pb[f][st] = tt;
+        }
+      }
+
+      // ---- O^T += V^T P^T over five 16-row d tiles ----------------------------------------------------------
+#pragma unroll
+      for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int d = 0; d < 5; ++d) {
+          const uint16_t* va = cV + (st * 32 + lq * 4 + (lr >> 2)) * RS + d * 16 + (lr & 3) * 4;
+          const u32x2 lo = lds_read_tr16(va);
+          const u32x2 hi = lds_read_tr16(va + 16 * RS);
+          const u32x4 vfrag = {lo.x, lo.y, hi.x, hi.y};
+          o_acc[0][d] = T::mfma32(vfrag, pb[0][st], o_acc[0][d]);
+          o_acc[1][d] = T::mfma32(vfrag, pb[1][st], o_acc[1][d]);
+        }
+    }
+
+    if (more) lstore(buf ^ 1);
+    __syncthreads();
+  }
+
+  // ---- normalise and store: lane (lq, lr) owns O[q = lr][d = 16 dd + 4 lq + r] ------------------------------
+  if (!active) return;
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    float l = l_run[f];
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.0f / l;
+    const int row = q0 + f * 16 + lr;
+    if (row < p.nq) {
+#pragma unroll
+      for (int d = 0; d < 5; ++d) {
+        const f32x4 o = o_acc[f][d] * inv;
+        *(u32x2*)(O + (int64_t)row * p.o_rs + d * 16 + lq * 4) = pack4<T>(o.x, o.y, o.z, o.w);
+      }
+    }
+  }
+}
+
+
+// =========================================================================================
 // History: r01 saw this kernel drift from run to run under `__launch_bounds__(256, 2)` and kept the default bounds
 // without a cause.  Root cause (r02, tools/determinism_probe.py located the first differing launch, the ISA showed
 // it): BF16::pack2 was an inline-asm `v_cvt_pk_bf16_f32`; with min-2-blocks bounds the MFMA results stay in VGPRs
@@ -411,6 +627,33 @@ extern "C" int vgen_attention(const vgen_attn_args* args, void* stream) {
   else
     hipLaunchKernelGGL(flash_kernel<F16>, dim3((unsigned)grid), dim3(256), 0, s, a, qtiles);
   return vgen_check_launch("attention(flash)");
+}
+
+extern "C" int vgen_attention_d80(const vgen_attn_args* args, void* stream) {
+  if (!args) {
+    vgen_set_error("attention_d80: null args");
+    return VGEN_E_BADARG;
+  }
+  const vgen_attn_args& a = *args;
+  VGEN_REQUIRE(a.dtype == VGEN_BF16 || a.dtype == VGEN_F16, "attention_d80: dtype");
+  VGEN_REQUIRE(a.heads > 0 && a.nq > 0 && a.nk > 0 && a.nbatch > 0 && a.inner > 0 && a.nbatch % a.inner == 0,
+               "attention_d80: bad sizes");
+  VGEN_REQUIRE(a.q && a.k && a.v && a.out, "attention_d80: null pointer");
+  VGEN_REQUIRE(vgen_aligned16(a.q) && vgen_aligned16(a.k) && vgen_aligned16(a.v) && vgen_aligned16(a.out),
+               "attention_d80: pointer alignment");
+  VGEN_REQUIRE((a.q_rs | a.q_bo | a.q_bi | a.k_rs | a.k_bo | a.k_bi | a.v_rs | a.v_bo | a.v_bi |
+                a.o_rs | a.o_bo | a.o_bi) % 8 == 0,
+               "attention_d80: strides must be multiples of 8 elements");
+  VGEN_REQUIRE(a.causal == 0, "attention_d80: causal masking is not supported (the image tower has no mask)");
+  const int qtiles = (a.nq + 127) / 128;
+  const int64_t grid = a.nbatch * a.heads * qtiles;
+  VGEN_REQUIRE(grid < (1LL << 31), "attention_d80: grid too large");
+  hipStream_t s = (hipStream_t)stream;
+  if (a.dtype == VGEN_BF16)
+    hipLaunchKernelGGL(flash_d80_kernel<BF16>, dim3((unsigned)grid), dim3(256), 0, s, a, qtiles);
+  else
+    hipLaunchKernelGGL(flash_d80_kernel<F16>, dim3((unsigned)grid), dim3(256), 0, s, a, qtiles);
+  return vgen_check_launch("attention_d80");
 }
 
 // =========================================================================================

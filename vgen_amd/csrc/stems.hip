@@ -172,6 +172,42 @@ __global__ __launch_bounds__(256) void frame_transformer_kernel(const float* __r
   }
 }
 
+
+// =========================================================================================
+// Patch embedding of the OpenCLIP image tower (ViT conv1: kernel = stride = patch, no bias) as the A operand of a tap-GEMM.
+// Rows [B * (cls + (H/P) * (W/P)), Kpad] 16-bit: row (b, cls + gy * (W/P) + gx) holds the patch at (gy, gx) of image b in
+// conv1.weight's K order (c, ky, kx), columns >= C*P*P zero; with cls = 1 every image's first row is all zero (the CLS slot:
+// the tap-GEMM's residual brings class_embedding + positional_embedding[0] there).  One thread per 8 output columns.
+template <typename T>
+__global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__ x, int C, int H, int W, int P, int Kpad,
+                                                       int cls, uint16_t* __restrict__ out, int64_t nchunks) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nchunks) return;
+  const int cpr = Kpad / 8;                       // 16-B chunks per row
+  const int k0 = (int)(i % cpr) * 8;
+  const int64_t row = i / cpr;
+  const int gw = W / P, tok = cls + (H / P) * gw;
+  const int64_t b = row / tok;
+  const int t = (int)(row % tok) - cls;
+  const int PP = P * P;
+  uint32_t v[4];
+#pragma unroll
+  for (int e = 0; e < 8; e += 2) {
+    float f[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int k = k0 + e + j;
+      f[j] = 0.f;
+      if (t >= 0 && k < C * PP) {
+        const int c = k / PP, ky = (k % PP) / P, kx = k % P;
+        const int y = (t / gw) * P + ky, xx = (t % gw) * P + kx;
+        f[j] = x[((b * C + c) * H + y) * (int64_t)W + xx];
+      }
+    }
+    v[e / 2] = pack2<T>(f[0], f[1]);
+  }
+  *(u32x4*)(out + row * Kpad + k0) = u32x4{v[0], v[1], v[2], v[3]};
+}
 }  // namespace
 
 extern "C" int vgen_conv3x3_small(const float* x, int64_t n, int32_t Cin, int32_t H, int32_t W, const float* w,
@@ -218,4 +254,28 @@ extern "C" int vgen_frame_transformer(const float* x, int64_t B, int32_t F, int3
   hipLaunchKernelGGL(frame_transformer_kernel, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, x, nseq, F,
                      (int)HW, P, y, last, out_scale, accumulate);
   return vgen_check_launch("frame_transformer");
+}
+
+extern "C" int vgen_patchify(const float* x, int64_t B, int32_t C, int32_t H, int32_t W, int32_t P, int32_t Kpad,
+                             int32_t cls, void* out, int32_t dtype, void* stream) {
+  VGEN_REQUIRE(x && out, "patchify: null pointer");
+  VGEN_REQUIRE(dtype == VGEN_BF16 || dtype == VGEN_F16, "patchify: dtype");
+  VGEN_REQUIRE(B > 0 && C > 0 && P > 0 && H >= P && W >= P && H % P == 0 && W % P == 0 && H <= 4096 && W <= 4096,
+               "patchify: image %dx%d is not a whole number of %dx%d patches", H, W, P, P);
+  VGEN_REQUIRE(cls == 0 || cls == 1, "patchify: cls must be 0 or 1");
+  VGEN_REQUIRE(Kpad % 8 == 0 && (int64_t)Kpad >= (int64_t)C * P * P && Kpad <= 65536,
+               "patchify: Kpad %d must be a multiple of 8 and >= C*P*P = %lld", Kpad, (long long)C * P * P);
+  VGEN_REQUIRE(vgen_aligned16(out), "patchify: output alignment");
+  const int64_t rows = B * (cls + (int64_t)(H / P) * (W / P));
+  const int64_t nchunks = rows * (Kpad / 8);
+  const int64_t grid = (nchunks + 255) / 256;
+  VGEN_REQUIRE(grid < (1LL << 31), "patchify: too large");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == VGEN_BF16)
+    hipLaunchKernelGGL(patchify_kernel<BF16>, dim3((unsigned)grid), dim3(256), 0, s, x, C, H, W, P, Kpad, cls,
+                       (uint16_t*)out, nchunks);
+  else
+    hipLaunchKernelGGL(patchify_kernel<F16>, dim3((unsigned)grid), dim3(256), 0, s, x, C, H, W, P, Kpad, cls,
+                       (uint16_t*)out, nchunks);
+  return vgen_check_launch("patchify");
 }

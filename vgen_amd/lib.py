@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("VGEN_HIP_LIB") or os.path.join(HERE, "libvgen_hip.so"
 VGEN_BF16, VGEN_F16, VGEN_F32 = 0, 1, 2
 TAP_LINEAR, TAP_CONV3X3, TAP_TEMPORAL3 = 0, 1, 2
 EPI_NONE, EPI_GEGLU = 0, 1
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class VgenHipError(RuntimeError):
@@ -71,11 +71,13 @@ SYMBOLS = {
     "vgen_tapgemm_query_plan": (C.c_int, [C.POINTER(TapGemmArgs), _vp]),
     "vgen_tapgemm_set_plans": (C.c_int, [_vp, _i32]),
     "vgen_attention": (C.c_int, [C.POINTER(AttnArgs), _vp]),
+    "vgen_attention_d80": (C.c_int, [C.POINTER(AttnArgs), _vp]),
     "vgen_softmax_rows": (C.c_int, [_vp, _i64, _i32, _i64, _f32, _vp, _i64, _i32, _vp]),
     "vgen_act_cast": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),
     "vgen_cast_split": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _vp]),
     "vgen_timestep_embedding": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp]),
     "vgen_conv3x3_small": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "vgen_patchify": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "vgen_adaptive_avgpool2d": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "vgen_frame_transformer": (C.c_int, [_vp, _i64, _i32, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _i32, _f32, _i32, _vp]),

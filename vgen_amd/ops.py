@@ -332,6 +332,24 @@ class HipBackend:
         _lib.check(rc, "vgen_attention")
         return g.out
 
+    def attention_d80(self, g: Attn):
+        """vgen_attention_d80: the same argument block, head_dim 80 (the CLIP image tower), non-causal."""
+        a = _lib.AttnArgs()
+        a.q, a.k, a.v, a.out = g.q.data_ptr(), g.k.data_ptr(), g.v.data_ptr(), g.out.data_ptr()
+        a.dtype, a.heads, a.nq, a.nk = _ENUM[g.q.dtype], g.heads, g.nq, g.nk
+        a.nbatch, a.inner = g.nbatch, g.inner
+        a.q_rs, a.q_bo, a.q_bi = g.q_s
+        a.k_rs, a.k_bo, a.k_bi = g.k_s
+        a.v_rs, a.v_bo, a.v_bi = g.v_s
+        a.o_rs, a.o_bo, a.o_bi = g.o_s
+        a.scale = float(g.scale)
+        a.causal = int(bool(g.causal))
+        with self._Prof("attention_d80", 4.0 * g.nbatch * g.heads * g.nq * g.nk * 80,
+                        (g.nbatch, g.heads, g.nq, g.nk)):
+            rc = self.lib.vgen_attention_d80(C.byref(a), self._stream(g.q))
+        _lib.check(rc, "vgen_attention_d80")
+        return g.out
+
     def softmax_rows(self, S, cols, scale, dt, out=None):
         S = _mat(S, "S")
         rows = S.shape[0]
@@ -379,6 +397,16 @@ class HipBackend:
                                          self._stream(x))
         _lib.check(rc, "vgen_conv3x3_small")
         return y
+
+    def patchify(self, x, P, Kpad, cls, dt):
+        """fp32 images [B, C, H, W] -> 16-bit patch rows [B * (cls + (H/P) * (W/P)), Kpad] (vgen_patchify)."""
+        assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
+        B, Cin, H, W = x.shape
+        out = torch.empty((B * (int(cls) + (H // P) * (W // P)), Kpad), dtype=dt, device=x.device)
+        rc = self.lib.vgen_patchify(_ptr(x), B, Cin, H, W, int(P), int(Kpad), int(cls), _ptr(out), _ENUM[dt],
+                                    self._stream(x))
+        _lib.check(rc, "vgen_patchify")
+        return out
 
     def adaptive_avgpool2d(self, x, Ho, Wo):
         assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4

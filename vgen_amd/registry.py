@@ -103,8 +103,9 @@ def _native_classes():
     from .unet_videolcm import UNetSD_TFT2V, UNetSD_VideoLCM
     from .vae import AutoencoderKL
     from .clip_text import FrozenOpenCLIPEmbedder
+    from .clip_visual import FrozenOpenCLIPTextVisualEmbedder
     return {"MODEL": [UNetSD_T2VBase, UNetSD_SR600, UNetSD_I2VGen, UNetSD_VideoLCM, UNetSD_TFT2V], "AUTO_ENCODER": [AutoencoderKL],
-            "DIFFUSION": [DiffusionDDIM, DiffusionDDIMSR], "EMBEDDER": [FrozenOpenCLIPEmbedder]}
+            "DIFFUSION": [DiffusionDDIM, DiffusionDDIMSR], "EMBEDDER": [FrozenOpenCLIPEmbedder, FrozenOpenCLIPTextVisualEmbedder]}
 
 
 def install(registries=None, quiet=True):
