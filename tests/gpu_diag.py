@@ -47,6 +47,21 @@ def main():
         run(f"im2col_bcfhw/{dtn}", lambda: kc.case_im2col(be, dev, dt, "bcfhw"))
         run(f"im2col_rows/{dtn}", lambda: kc.case_im2col(be, dev, dt, "rows"))
     run("pointwise", lambda: kc.case_pointwise(be, dev))
+    # the adversarial attention cases (tests/attn_cases.py): worst |err| / bound per case against the fp64 reference
+    import attn_cases as ac
+    from test_attention_edges import _launch
+
+    def edge(kernel, shape, dt, fam):
+        case = ac.build(kernel, shape, dt, fam)
+        O, bnd = ac.case_reference(case)
+        got = case.operand("out", _launch(be, case))
+        return {"out": {"rel_l2": ac.rel_l2(got, O), "worst_over_bound": ac.worst_ratio(got, O, bnd)}}
+
+    for dtn, dt in kc.DTS.items():
+        for kernel in ac.KERNELS:
+            for fam in ac.FAMILIES:
+                for shape in ac.shapes_for(kernel, fam):
+                    run(f"attn_edges/{kernel}/{dtn}/{fam}/{'_'.join(map(str, shape))}", lambda a=(kernel, shape, dt, fam): edge(*a))
     run("gaussian", lambda: kc.case_gaussian(be, dev))
     for mt in (0, 1, 2):
         for eta in (0.0, 0.7):
