@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VGEN_ABI_VERSION 6
+#define VGEN_ABI_VERSION 7
 
 enum { VGEN_BF16 = 0, VGEN_F16 = 1, VGEN_F32 = 2 };
 
@@ -407,6 +407,34 @@ int vgen_frame_transformer(const float* x, int64_t B, int32_t F, int32_t d, int6
  * image; mean / stdv: C device floats.  Bit-exact with the reference arithmetic (fp32, truncation). */
 int vgen_frames_u8(const float* x, int64_t rows, int32_t C, int64_t ldx, const float* mean,
                    const float* stdv, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * DreamVideo Adapter (tools/modules/unet/util.py:499-519; its call sites in BasicTransformerBlockWithAdapter,
+ * util.py:641-672) — down-projection, exact GELU, up-projection and the identity in ONE launch; the hidden
+ * activation never reaches memory:
+ *
+ *   out[m, n] = x[m, n] + bu[n] + sum_j Wu[n, j] * r16( gelu_erf( hb[m / rows_per_hb, j] + sum_k Wd[j, k] * r16(x[m, k]) ) )
+ *
+ *   x, out  fp32 rows [M, d], row strides ldx / ldo (elements, multiples of 4, >= d).  out may alias x ONLY as the exact
+ *           in-place form (out == x and ldo == ldx: a block reads all it needs of its own rows before it writes them);
+ *           any other overlap of the two row ranges is rejected with VGEN_E_BADARG.
+ *   Wd      [hp, d], Wu [d, hp]: `dtype` (VGEN_BF16 | VGEN_F16), contiguous, packed once per weight load.  h = the
+ *           adapter's hidden width (a multiple of 8), hp = h rounded up to a multiple of 32 (<= 640); rows h..hp of Wd,
+ *           columns h..hp of Wu and of hb are ZERO (gelu(0) = 0: the padding contributes nothing).
+ *   bu      fp32 [d]: up_linear.bias.
+ *   hb      fp32 [ceil(M / rows_per_hb), hp], row stride ldhb: the hidden ROW BIAS.  It carries down_linear.bias and
+ *           the condition: down(x + lam (Wc c + bc)) = down(x) + lam Wd (Wc c + bc), so hb = b_down + lam Wd_fp32 (Wc c + bc)
+ *           is a constant of the prompt, evaluated once in fp32 (vgen_linear_f32).  Temporal adapters: rows are
+ *           (unit, frame, pixel) and rows_per_hb = H * W; unconditioned adapters: one row, rows_per_hb >= M.
+ *   r16     round-to-nearest-even to `dtype`, at the two marked places and nowhere else; both products accumulate in
+ *           fp32 on the matrix units; gelu_erf is the exact-erf GELU (libm erff, F.gelu's default).
+ *   fp16:   r16(x) of an un-normalised token stream overflows to inf exactly where the reference's autocast F.linear
+ *           does (|x| > 65504); the reference's behaviour is kept — no clamp.
+ *   d % 64 == 0, d <= 1280; M arbitrary (rows >= M are neither read nor written, nor any column >= d); every pointer
+ *   16-byte aligned.  Argument errors return VGEN_E_BADARG before anything is launched. */
+int vgen_adapter(const float* x, int64_t ldx, int64_t M, int32_t d, int32_t h, int32_t hp, const void* Wd,
+                 const void* Wu, const float* bu, const float* hb, int64_t ldhb, int64_t rows_per_hb, float* out,
+                 int64_t ldo, int32_t dtype, void* stream);
 
 /* Glue of a sampling session's step graph (vgen_amd/session.py), so that a captured step holds only this library's
  * launches.  vgen_repeat_rows: dst[g*bytes .. (g+1)*bytes) = src[0 .. bytes) for g < G — the rows of the context-free

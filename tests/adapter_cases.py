@@ -1,0 +1,98 @@
+"""vgen_adapter: operands, the fp64 reference and the derived per-element bound (tests/test_dreamvideo.py).
+
+The kernel computes   out = x + bu + Wu . r16(gelu(hb[row] + Wd . r16(x)))   with fp32 accumulation.  Against an fp64
+evaluation of the SAME 16-bit operands, with the hidden activation rounded at the same place, an output element may
+deviate by (u32 = 2^-24; the 16-bit format enters only through its own rounding function r16):
+
+  pre-activation   |ds|  <= e_s = (d + 2) u32 (|hb| + sum_k |Wd| |r16(x)|)        any summation order of d products + bias
+  gate             |dg|  <= e_g = L e_s + 20 u32 |s| + 2 u32 |g|                  L = max gelu' = 1.13 (at s = sqrt 2); libm
+                                                                                  erff to the 16 ulp OpenCL allows (abs 32 u32
+                                                                                  on |erf| <= 1, times |s| / 2), the three fp32
+                                                                                  products / the sum of 0.5 s (1 + erf): 4 u32
+                                                                                  |s|; 2 u32 |g|: fp64 -> fp32 of g itself
+  hidden           |dh|  <= e_h = r16(g + e_g) - r16(g - e_g)                     r16 is monotone: zero unless the interval
+                                                                                  straddles a rounding boundary — then the
+                                                                                  gap between the two 16-bit values (one ulp)
+  output           |do|  <= sum_j |Wu| e_h + (hp + 3) u32 (sum_j |Wu| (|h16| + e_h) + |bu| + |x|)
+
+Nothing here is fitted to what a device returns; the statistic is worst = max |err| / bound <= 1."""
+import torch
+
+U32 = 2.0 ** -24
+GELU_LIP = 1.13
+# (M, d, h): the four full-size shapes of the joint configuration at [2 units, 32 frames, 32 x 32] (+ the 4 x 4 level),
+# ragged tails, and the tiny fixtures' widths
+FULL_SHAPES = [(65536, 320, 160), (65536, 512, 256), (16384, 640, 320), (4096, 1280, 640), (1024, 1280, 640)]
+RAGGED_SHAPES = [(4099, 320, 160), (1001, 1280, 640), (77, 640, 320), (1, 64, 32)]
+TINY_SHAPES = [(1024, 128, 64), (512, 64, 32), (520, 128, 24)]
+
+
+def hp_of(h):
+    return (h + 31) // 32 * 32
+
+
+def gelu64(s):
+    return 0.5 * s * (1.0 + torch.erf(s * 0.7071067811865476))
+
+
+def operands(M, d, h, dt, rows_per_hb, seed=0, device="cpu", x_scale=2.0):
+    """Seeded operands of one launch.  x is an un-normalised token stream (N(0, x_scale) with a per-column offset),
+    weights ~ N(0, 1 / fan_in) rounded to dt and zero-padded to hp, hb of the size of a down_linear output."""
+    g = torch.Generator("cpu").manual_seed(seed * 7919 + M + 31 * d + 17 * h)
+    hp = hp_of(h)
+    x = torch.randn(M, d, generator=g) * x_scale + torch.randn(1, d, generator=g)
+    wd = torch.zeros(hp, d)
+    wd[:h] = torch.randn(h, d, generator=g) / d ** 0.5
+    wu = torch.zeros(d, hp)
+    wu[:, :h] = torch.randn(d, h, generator=g) / h ** 0.5
+    bu = 0.1 * torch.randn(d, generator=g)
+    nhb = (M + rows_per_hb - 1) // rows_per_hb
+    hb = torch.zeros(nhb, hp)
+    hb[:, :h] = torch.randn(nhb, h, generator=g)
+    to = lambda t: t.to(device)
+    return dict(x=to(x), wd=to(wd.to(dt)), wu=to(wu.to(dt)), bu=to(bu), hb=to(hb), rows_per_hb=rows_per_hb, h=h, dt=dt)
+
+
+def reference_and_bound(op):
+    """(fp64 reference [M, d], per-element bound [M, d]) of vgen_adapter on `op` (any device)."""
+    dt, x = op["dt"], op["x"]
+    M, d = x.shape
+    hp = op["wd"].shape[0]
+    r16 = lambda v: v.float().to(dt).double()
+    idx = torch.arange(M, device=x.device) // op["rows_per_hb"]
+    wd, wu = op["wd"].double(), op["wu"].double()
+    xr = x.to(dt).double()
+    hb = op["hb"].double()[idx]
+    s = hb + xr @ wd.t()
+    e_s = (d + 2) * U32 * (hb.abs() + xr.abs() @ wd.abs().t())
+    g = gelu64(s)
+    e_g = GELU_LIP * e_s + 20 * U32 * s.abs() + 2 * U32 * g.abs()
+    h16 = r16(g)
+    e_h = r16(g + e_g) - r16(g - e_g)
+    assert bool((e_h >= 0).all())
+    xd, bu = x.double(), op["bu"].double()
+    ref = xd + bu + h16 @ wu.t()
+    flip = e_h @ wu.abs().t()
+    bound = flip + (hp + 3) * U32 * ((h16.abs() + e_h) @ wu.abs().t() + bu.abs() + xd.abs())
+    return ref, bound
+
+
+def model(op, mistake=None):
+    """The kernel's arithmetic restated in fp32 torch (CPU model), optionally with one modelled mistake."""
+    dt, x = op["dt"], op["x"]
+    M = x.shape[0]
+    idx = torch.arange(M, device=x.device) // op["rows_per_hb"]
+    if mistake == "hb_wrong_frame":
+        idx = (idx + 1) % op["hb"].shape[0]
+    s = x.to(dt).float() @ op["wd"].float().t() + op["hb"][idx]
+    if mistake == "hidden_16bit_accumulate":
+        s = s.to(dt).float()
+    if mistake == "tanh_gelu":
+        g = 0.5 * s * (1.0 + torch.tanh(0.7978845608028654 * (s + 0.044715 * s ** 3)))
+    else:
+        g = 0.5 * s * (1.0 + torch.erf(s * 0.7071067811865476))
+    return x + op["bu"] + g.to(dt).float() @ op["wu"].float().t()
+
+
+def worst_ratio(out, ref, bound):
+    return float(((out.double() - ref).abs() / bound).max())

@@ -1,0 +1,242 @@
+// adapter.hip — the DreamVideo Adapter (tools/modules/unet/util.py:499-519, used at :641-672) as ONE launch:
+//
+//   out[m, n] = x[m, n] + bu[n] + sum_j Wu[n, j] * r16( gelu_erf( hb[m / rows_per_hb, j] + sum_k Wd[j, k] * r16(x[m, k]) ) )
+//
+// The operator is memory-bound (level 0 of the UNet: 65 536 rows x 320 fp32 in and out, 13 GFLOP), so the hidden
+// activation never leaves the CU.  Tile plan (one block = 256 threads = 4 waves, BM = 16 * MF rows, MF in {1, 2, 4}):
+//   phase 1  hidden[BM, hp] = x_tile . Wd^T.  x streams through a double-buffered LDS image of [BM rows x 64 k] 16-bit
+//            (coalesced fp32 float4 loads, rounded once, one barrier per K-tile); the waves split the HIDDEN columns
+//            (16-column fragments wave, wave + 4, ...: NFW per wave), so Wd is read once per block, each wave straight from
+//            L2 in MFMA operand layout, and the fp32 hidden tile lives in MF x NFW accumulator fragments (<= 80 VGPRs).
+//   gate     + hb row, exact-erf GELU (libm erff), r16, 8-byte stores into the LDS image hs[BM][hp + 8].
+//   phase 2  the waves split the OUTPUT columns in groups of 32 (whole 128-byte lines of a row): acc = Wu . hs^T over hp,
+//            then out = acc + bu + x (fp32 float4 loads / stores; the residual re-read of x hits L2).
+// Operand swap as in tapgemm.hip (D[n][m]: a lane holds 4 consecutive columns of ONE row), so every global / LDS access
+// of an epilogue is 8 or 16 contiguous bytes.  LDS: 288 * BM + 2 * BM * (hp + 8) bytes <= 60 416 (MF = 4 is only taken
+// for hp <= 320), no scratch, no dynamic indexing of register arrays.
+// Rows >= M: their loads are clamped to row M - 1 (never beyond the caller's buffers), nothing is stored for them.
+// In-place (out == x, ldo == ldx) is safe: a block reads and writes only its own rows, and every element of x is read
+// (phase 1 completely, the residual by the lane that overwrites it) before it is written.
+#include "common.h"
+
+namespace {
+
+constexpr int AD_KC = 5;         // k-steps of phase 2 whose weight fragments are loaded ahead of their MFMAs (hp / 32 = 5, 10, 20)
+constexpr int AD_XS_LD = 72;     // 64 k + 8 pad, 16-bit elements: 144-byte rows (ds_read_b128 rows land on distinct banks)
+
+struct adapter_params {
+  const float* x;
+  int64_t ldx;
+  float* out;
+  int64_t ldo;
+  int64_t M;
+  int d, hp;
+  const uint16_t* Wd;
+  const uint16_t* Wu;
+  const float* bu;
+  const float* hb;
+  int64_t ldhb, rows_per_hb;
+};
+
+template <typename T, int MF, int NFW>
+__global__ __launch_bounds__(256) void adapter_kernel(const adapter_params p) {
+  constexpr int BM = 16 * MF;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint16_t* const xs = (uint16_t*)smem;              // [2][BM][AD_XS_LD]
+  uint16_t* const hs = xs + 2 * BM * AD_XS_LD;       // [BM][hp + 8]
+  const int d = p.d, hp = p.hp;
+  const int hs_ld = hp + 8;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lq = lane >> 4;
+  const int64_t m0 = (int64_t)blockIdx.x * BM;
+  const int64_t last = p.M - 1;
+  const int nhf = hp >> 4;                           // 16-column fragments of the hidden tile
+
+  // ---- phase 1: hidden = x . Wd^T --------------------------------------------------------------------------------
+  const int xrow = tid >> 4, xc4 = tid & 15;         // thread -> (row xrow + 16 t, floats 4 xc4 ..) of a [BM x 64] tile
+  const float* xsrc[MF];
+#pragma unroll
+  for (int t = 0; t < MF; ++t) {
+    const int64_t gr = m0 + xrow + 16 * t;
+    xsrc[t] = p.x + (gr < last ? gr : last) * p.ldx + xc4 * 4;
+  }
+  f32x4 xr[MF];
+  auto xload = [&](int kt) __attribute__((always_inline)) {
+#pragma unroll
+    for (int t = 0; t < MF; ++t) xr[t] = *(const f32x4*)(xsrc[t] + kt * 64);
+  };
+  auto xstore = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int t = 0; t < MF; ++t)
+      *(u32x2*)(xs + (buf * BM + xrow + 16 * t) * AD_XS_LD + xc4 * 4) = pack4<T>(xr[t][0], xr[t][1], xr[t][2], xr[t][3]);
+  };
+
+  f32x4 acc[MF][NFW];
+#pragma unroll
+  for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+    for (int f = 0; f < NFW; ++f) acc[mf][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  xload(0);
+  xstore(0);
+  __syncthreads();
+  const int nkt = d >> 6;
+  const uint16_t* const wd_lane = p.Wd + (int64_t)lr * d + lq * 8;
+  for (int kt = 0; kt < nkt; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nkt) xload(kt + 1);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      u32x4 bx[MF];
+#pragma unroll
+      for (int mf = 0; mf < MF; ++mf)
+        bx[mf] = *(const u32x4*)(xs + (cur * BM + mf * 16 + lr) * AD_XS_LD + ks * 32 + lq * 8);
+#pragma unroll
+      for (int f = 0; f < NFW; ++f) {
+        const int hf = wave + 4 * f;
+        if (hf < nhf) {
+          const u32x4 a = *(const u32x4*)(wd_lane + (int64_t)hf * 16 * d + kt * 64 + ks * 32);
+#pragma unroll
+          for (int mf = 0; mf < MF; ++mf) acc[mf][f] = T::mfma32(a, bx[mf], acc[mf][f]);
+        }
+      }
+    }
+    if (kt + 1 < nkt) xstore(cur ^ 1);
+    __syncthreads();
+  }
+
+  // ---- gate: + hidden row bias, exact GELU, round, into LDS --------------------------------------------------------
+  {
+    const float* hbrow[MF];
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf) {
+      const int64_t gm = m0 + mf * 16 + lr;
+      hbrow[mf] = p.hb + ((gm < last ? gm : last) / p.rows_per_hb) * p.ldhb + lq * 4;
+    }
+#pragma unroll
+    for (int f = 0; f < NFW; ++f) {
+      const int hf = wave + 4 * f;
+      if (hf < nhf) {
+#pragma unroll
+        for (int mf = 0; mf < MF; ++mf) {
+          const f32x4 v = acc[mf][f] + *(const f32x4*)(hbrow[mf] + hf * 16);
+          *(u32x2*)(hs + (mf * 16 + lr) * hs_ld + hf * 16 + lq * 4) =
+              pack4<T>(gelu_erf_exact(v[0]), gelu_erf_exact(v[1]), gelu_erf_exact(v[2]), gelu_erf_exact(v[3]));
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 2: out = x + bu + hidden16 . Wu^T ------------------------------------------------------------------------
+  const int ngr = d >> 5;
+  const uint16_t* const wu_lane = p.Wu + (int64_t)lr * hp + lq * 8;
+  for (int g = wave; g < ngr; g += 4) {
+    f32x4 o[MF][2];
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf) o[mf][0] = o[mf][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // AD_KC k-steps per round: their 2 * AD_KC weight fragments are all in flight before the first MFMA needs one (a
+    // round of 2 loads -> 2 MF MFMAs left the wave waiting one L2 latency per 32 hidden columns)
+    const uint16_t* const wu_g = wu_lane + (int64_t)g * 32 * hp;
+    for (int k0 = 0; k0 < hp; k0 += 32 * AD_KC) {
+      u32x4 a[AD_KC][2];
+#pragma unroll
+      for (int kk = 0; kk < AD_KC; ++kk) {
+        if (k0 + kk * 32 < hp) {
+#pragma unroll
+          for (int nb = 0; nb < 2; ++nb) a[kk][nb] = *(const u32x4*)(wu_g + (int64_t)nb * 16 * hp + k0 + kk * 32);
+        }
+      }
+#pragma unroll
+      for (int kk = 0; kk < AD_KC; ++kk) {
+        if (k0 + kk * 32 < hp) {
+          u32x4 bh[MF];
+#pragma unroll
+          for (int mf = 0; mf < MF; ++mf) bh[mf] = *(const u32x4*)(hs + (mf * 16 + lr) * hs_ld + k0 + kk * 32 + lq * 8);
+#pragma unroll
+          for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+            for (int mf = 0; mf < MF; ++mf) o[mf][nb] = T::mfma32(a[kk][nb], bh[mf], o[mf][nb]);
+        }
+      }
+    }
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf) {
+      const int64_t gm = m0 + mf * 16 + lr;
+      if (gm < p.M) {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+          const int n = g * 32 + nb * 16 + lq * 4;
+          const f32x4 xv = *(const f32x4*)(p.x + gm * p.ldx + n);
+          const f32x4 b = *(const f32x4*)(p.bu + n);
+          *(f32x4*)(p.out + gm * p.ldo + n) = o[mf][nb] + b + xv;
+        }
+      }
+    }
+  }
+}
+
+template <typename T, int MF, int NFW>
+int launch_adapter(const adapter_params& p, hipStream_t s) {
+  constexpr int BM = 16 * MF;
+  const int64_t grid = (p.M + BM - 1) / BM;
+  const size_t lds = (size_t)2 * BM * AD_XS_LD * 2 + (size_t)BM * (p.hp + 8) * 2;
+  hipLaunchKernelGGL((adapter_kernel<T, MF, NFW>), dim3((unsigned)grid), dim3(256), lds, s, p);
+  return vgen_check_launch("adapter");
+}
+
+template <typename T, int NFW>
+int pick_mf(const adapter_params& p, hipStream_t s) {
+  // the largest row tile that still gives every second CU a block (a larger tile re-reads the weights less often);
+  // 64 rows only where the hidden accumulators stay <= 80 VGPRs and the LDS image <= 60 KiB (hp <= 320)
+  const int64_t want = vgen_device_cus() / 2;
+  if constexpr (NFW <= 5) {
+    if ((p.M + 63) / 64 >= want) return launch_adapter<T, 4, NFW>(p, s);
+  }
+  if ((p.M + 31) / 32 >= want) return launch_adapter<T, 2, NFW>(p, s);
+  return launch_adapter<T, 1, NFW>(p, s);
+}
+
+template <typename T>
+int pick_nfw(const adapter_params& p, hipStream_t s) {
+  const int need = ((p.hp >> 4) + 3) / 4;            // hidden fragments per wave
+  if (need <= 1) return pick_mf<T, 1>(p, s);
+  if (need <= 2) return pick_mf<T, 2>(p, s);
+  if (need <= 3) return pick_mf<T, 3>(p, s);
+  if (need <= 4) return pick_mf<T, 4>(p, s);
+  if (need <= 5) return pick_mf<T, 5>(p, s);
+  return pick_mf<T, 10>(p, s);
+}
+
+}  // namespace
+
+extern "C" int vgen_adapter(const float* x, int64_t ldx, int64_t M, int32_t d, int32_t h, int32_t hp, const void* Wd,
+                            const void* Wu, const float* bu, const float* hb, int64_t ldhb, int64_t rows_per_hb,
+                            float* out, int64_t ldo, int32_t dtype, void* stream) {
+  VGEN_REQUIRE(dtype == VGEN_BF16 || dtype == VGEN_F16, "adapter: dtype must be VGEN_BF16 or VGEN_F16");
+  VGEN_REQUIRE(x && out && Wd && Wu && bu && hb, "adapter: x, out, Wd, Wu, bu and hb must be non-null");
+  VGEN_REQUIRE(d > 0 && d % 64 == 0 && d <= 1280, "adapter: d = %d must be a multiple of 64, <= 1280", (int)d);
+  VGEN_REQUIRE(h > 0 && h % 8 == 0, "adapter: hidden width h = %d must be a positive multiple of 8", (int)h);
+  VGEN_REQUIRE(hp == (h + 31) / 32 * 32 && hp <= 640, "adapter: hp = %d must be h = %d rounded up to a multiple of 32, <= 640",
+               (int)hp, (int)h);
+  VGEN_REQUIRE(M >= 0 && M < (1LL << 34), "adapter: M out of range");
+  VGEN_REQUIRE(ldx >= d && ldo >= d && ldx % 4 == 0 && ldo % 4 == 0, "adapter: row strides must be >= d and multiples of 4");
+  VGEN_REQUIRE(ldhb >= hp && ldhb % 4 == 0 && rows_per_hb >= 1, "adapter: ldhb >= hp, ldhb %% 4 == 0, rows_per_hb >= 1");
+  VGEN_REQUIRE(vgen_aligned16(x) && vgen_aligned16(out) && vgen_aligned16(Wd) && vgen_aligned16(Wu) && vgen_aligned16(bu) &&
+                   vgen_aligned16(hb),
+               "adapter: every pointer must be 16-byte aligned");
+  if (M == 0) return 0;
+  if (!((const void*)out == (const void*)x && ldo == ldx)) {
+    // anything but the exact in-place form must not overlap: another block's rows would be overwritten under its reads
+    const uintptr_t xb = (uintptr_t)x, xe = xb + (size_t)((M - 1) * ldx + d) * 4;
+    const uintptr_t ob = (uintptr_t)out, oe = ob + (size_t)((M - 1) * ldo + d) * 4;
+    VGEN_REQUIRE(oe <= xb || xe <= ob, "adapter: out overlaps x (only out == x with ldo == ldx may alias)");
+  }
+  adapter_params p;
+  p.x = x; p.ldx = ldx; p.out = out; p.ldo = ldo; p.M = M; p.d = d; p.hp = hp;
+  p.Wd = (const uint16_t*)Wd; p.Wu = (const uint16_t*)Wu; p.bu = bu; p.hb = hb; p.ldhb = ldhb; p.rows_per_hb = rows_per_hb;
+  hipStream_t s = (hipStream_t)stream;
+  return dtype == VGEN_BF16 ? pick_nfw<BF16>(p, s) : pick_nfw<F16>(p, s);
+}

@@ -385,6 +385,30 @@ class HipBackend:
         _lib.check(rc, "vgen_cast_split")
         return out
 
+    def adapter(self, x, Wd, Wu, bu, hb, rows_per_hb, h, out=None):
+        """x + up(gelu(down(x) + hb[row // rows_per_hb])) in one launch (vgen_adapter).  x fp32 [M, d] view; Wd [hp, d] /
+        Wu [d, hp] 16-bit contiguous (hp = h padded to 32, padding zero); bu fp32 [d]; hb fp32 2-D view [>= ceil(M /
+        rows_per_hb), hp].  out: fp32 [M, d] view (default new; may be x itself)."""
+        x = _mat(x, "x")
+        hb = _mat(hb, "hb")
+        M, d = x.shape
+        hp = Wd.shape[0]
+        assert x.dtype == torch.float32 and hb.dtype == torch.float32 and bu.dtype == torch.float32 and bu.is_contiguous()
+        assert Wd.dtype == Wu.dtype and Wd.is_contiguous() and Wu.is_contiguous()
+        assert Wd.shape == (hp, d) and Wu.shape == (d, hp) and bu.shape == (d,) and hb.shape[1] == hp
+        assert hb.shape[0] * int(rows_per_hb) >= M, (tuple(hb.shape), rows_per_hb, M)
+        if out is None:
+            out = torch.empty((M, d), dtype=torch.float32, device=x.device)
+        _mat(out, "out")
+        assert out.dtype == torch.float32 and out.shape == (M, d)
+        # algorithmic bytes: x read + out written in fp32, both weights once
+        with self._Prof("adapter", 4.0 * M * d * hp, (M, d, hp), (8.0 * M * d + 4.0 * d * hp, 4.0 * M * d * hp)):
+            rc = self.lib.vgen_adapter(_ptr(x), x.stride(0), M, d, int(h), hp, _ptr(Wd), _ptr(Wu), _ptr(bu), _ptr(hb),
+                                       hb.stride(0), int(rows_per_hb), _ptr(out), out.stride(0), _ENUM[Wd.dtype],
+                                       self._stream(x))
+        _lib.check(rc, "vgen_adapter")
+        return out
+
     # -- condition stems (fp32, NCHW frames; once per sampling session) ------------------------------------
     def conv3x3_small(self, x, w, b, stride=1, act=0):
         assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4

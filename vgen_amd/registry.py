@@ -101,10 +101,12 @@ def _native_classes():
     from .unet import UNetSD_SR600, UNetSD_T2VBase
     from .unet_i2vgen import UNetSD_I2VGen
     from .unet_videolcm import UNetSD_TFT2V, UNetSD_VideoLCM
+    from .unet_dreamvideo import UNetSD_DreamVideo
     from .vae import AutoencoderKL
     from .clip_text import FrozenOpenCLIPEmbedder
     from .clip_visual import FrozenOpenCLIPTextVisualEmbedder
-    return {"MODEL": [UNetSD_T2VBase, UNetSD_SR600, UNetSD_I2VGen, UNetSD_VideoLCM, UNetSD_TFT2V], "AUTO_ENCODER": [AutoencoderKL],
+    return {"MODEL": [UNetSD_T2VBase, UNetSD_SR600, UNetSD_I2VGen, UNetSD_VideoLCM, UNetSD_TFT2V,
+                      UNetSD_DreamVideo], "AUTO_ENCODER": [AutoencoderKL],
             "DIFFUSION": [DiffusionDDIM, DiffusionDDIMSR], "EMBEDDER": [FrozenOpenCLIPEmbedder, FrozenOpenCLIPTextVisualEmbedder]}
 
 

@@ -83,6 +83,32 @@ def _kw_struct(kwargs_list):
     return tuple(tuple((k, _val_struct(kw[k])) for k in sorted(kw)) for kw in kwargs_list)
 
 
+def _map_tensors(o, fn):
+    """`fn` over the tensors of a (nested) dict; None stays None."""
+    if o is None:
+        return None
+    if torch.is_tensor(o):
+        return fn(o)
+    return {k: _map_tensors(v, fn) for k, v in o.items()}
+
+
+def _struct_of(o):
+    if o is None or torch.is_tensor(o):
+        return None if o is None else (tuple(o.shape), o.dtype)
+    return tuple((k, _struct_of(o[k])) for k in sorted(o))
+
+
+def _copy_tensors(dst, src):
+    """src -> dst in place, tensor by tensor (same structure: the captured graphs read dst by address)."""
+    if dst is None:
+        return
+    if torch.is_tensor(dst):
+        dst.copy_(src)
+        return
+    for k in dst:
+        _copy_tensors(dst[k], src[k])
+
+
 class UnitSession:
     def __init__(self, model, shape, device, kwargs_list, t_dtype=torch.long, num_timesteps=None,
                  units: Optional[Sequence[int]] = None):
@@ -102,7 +128,7 @@ class UnitSession:
         self._idx = torch.tensor(sel, dtype=torch.long, device=self.device)
         C_stem = model._stem_channels()
         self.x_units = torch.zeros((nU, C_stem, self.F, self.H, self.W), dtype=torch.float32, device=self.device)
-        self.kv = self.fps = None
+        self.kv = self.fps = self.body = None
         self.per_frame, self.Lctx, self.shared = False, 0, 1
         if not self._bind(kwargs_list, first=True):
             raise ValueError("kwarg sets cannot share one UNet batch")
@@ -150,10 +176,12 @@ class UnitSession:
             ctx = ctx[idx]
         shared = model.shared_prefix_groups(prep, self.G, self.B) if self.full else 1
         fps = None if prep["fps"] is None else prep["fps"].to(dev)[idx].contiguous()
+        # a model's own prompt constants for its _body (optional "body" entry: unit-major tensors, possibly in dicts)
+        body = _map_tensors(prep.get("body"), lambda v: v.to(dev)[idx].contiguous())
         if not first:
             # the launch sequence of the captured graphs is a function of these: a prompt that changes them needs its own session
             if per_frame != self.per_frame or ctx.shape[1] != self.Lctx or shared != self.shared or \
-                    (fps is None) != (self.fps is None):
+                    (fps is None) != (self.fps is None) or _struct_of(body) != _struct_of(self.body):
                 return False
         # everything that can fail (allocations, the K/V GEMM) runs BEFORE the first write into a buffer a graph reads
         kv = model._context_kv(ctx.contiguous(), dev) if nU else None   # prompt constant: once per prompt
@@ -162,13 +190,14 @@ class UnitSession:
         if extra is not None:
             self.x_units[:, self.C_lat:] = extra.to(dev).float()[idx]
         if first:
-            self.kv, self.fps = kv, fps
+            self.kv, self.fps, self.body = kv, fps, body
             self.per_frame, self.Lctx, self.shared = per_frame, ctx.shape[1], shared
         else:
             if kv is not None:
                 self.kv.copy_(kv)
             if fps is not None:
                 self.fps.copy_(fps)
+            _copy_tensors(self.body, body)
         self.kwargs_ref = [dict(kw) for kw in kwargs_list]         # keeps the keyed tensors alive (ids stay unique)
         self._last_out = None
         return True
@@ -197,7 +226,8 @@ class UnitSession:
             emb = ops.backend().gather_rows_f32(self.emb_tab, self.t_units)
         else:
             emb = m._embed(self.t_units, self.fps, nU, self.device)
-        m._body(self.x_units, emb, self.kv, self.Lctx, self.per_frame, out=self.out, shared_groups=self.shared)
+        m._body(self.x_units, emb, self.kv, self.Lctx, self.per_frame, out=self.out, shared_groups=self.shared,
+                **(self.body or {}))
 
     def _run(self, key, launches, graph_ok=True):
         """Run `launches()` eagerly (first call: warms the allocator, JIT-free) and from then on as a graph.

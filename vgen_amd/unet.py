@@ -684,20 +684,26 @@ class UNetSD_T2VBase(nn.Module):
                                    colstats=M >= ops.COLSTATS_MIN_ROWS))
         return t
 
-    def _tblock(self, P, x, M, d, heads, attn1, attn2):
+    def _adapt(self, T, slot, tok, M, geom=None):
+        """Hook at the three residual joins of a transformer block (slot "a1" | "a2" | "ff"): the tensor the branch's
+        out-projection adds to.  The t2v trunk has nothing there; UNetSD_DreamVideo runs its parallel adapters here
+        (vgen_amd/unet_dreamvideo.py).  T: the block's packed dict; geom: (units, F, H*W) of a temporal block's rows."""
+        return tok
+
+    def _tblock(self, P, x, M, d, heads, attn1, attn2, geom=None):
         """reference: BasicTransformerBlock.forward (util.py:700-704); x is the fp32 token stream."""
         be = ops.backend()
         dt = self.compute_dtype
         n = be.layernorm(x, *P["ln1"], 1e-5, dt)
         qkv = self._linear(n, P["qkv1"], M, out_dtype=dt)
         o = attn1(qkv)
-        x = self._linear(o, P["o1"], M, residual=x)
+        x = self._linear(o, P["o1"], M, residual=self._adapt(P, "a1", x, M, geom))
         n = be.layernorm(x, *P["ln2"], 1e-5, dt)
         o = attn2(n)
-        x = self._linear(o, P["o2"], M, residual=x)
+        x = self._linear(o, P["o2"], M, residual=self._adapt(P, "a2", x, M, geom))
         n = be.layernorm(x, *P["ln3"], 1e-5, dt)
         g = self._linear(n, P["ff1"], M, out_dtype=dt, epilogue=L.EPI_GEGLU)
-        return self._ff_out(g, P["ff2"], M, x)
+        return self._ff_out(g, P["ff2"], M, self._adapt(P, "ff", x, M, geom))
 
     def _ff_out(self, g, ff2, M, tok):
         """tok + FF-out, as the A operand of proj_out: emitted 16-bit straight from the GEMM's epilogue (sum formed in fp32)
@@ -731,7 +737,7 @@ class UNetSD_T2VBase(nn.Module):
         ld = 3 * d
         be.attention(Attn(q=qkv, k=qkv[:, d:], v=qkv[:, 2 * d:], out=o, heads=heads, nq=N, nk=N, nbatch=Bp * F, inner=1,
                           q_s=(ld, N * ld, 0), k_s=(ld, N * ld, 0), v_s=(ld, N * ld, 0), o_s=(d, N * d, 0), scale=scale))
-        tok = self._linear(o, T["o1"], Mp, residual=tok)
+        tok = self._linear(o, T["o1"], Mp, residual=self._adapt(T, "a1", tok, Mp))
         # x = x + attn2(norm2(x), context): the query side first — the last context-free step
         n = be.layernorm(tok, *T["ln2"], 1e-5, dt)
         q = self._linear(n, T["q2"], Mp, out_dtype=dt)
@@ -746,11 +752,11 @@ class UNetSD_T2VBase(nn.Module):
         kvs = (kw, F * Lctx * kw, Lctx * kw) if kv_per_frame else (kw, Lctx * kw, 0)
         be.attention(Attn(q=q, k=k, v=v, out=o, heads=heads, nq=N, nk=Lctx, nbatch=B * F, inner=F,
                           q_s=(d, F * N * d, N * d), k_s=kvs, v_s=kvs, o_s=(d, F * N * d, N * d), scale=scale))
-        tok = self._linear(o, T["o2"], M, residual=tok)
+        tok = self._linear(o, T["o2"], M, residual=self._adapt(T, "a2", tok, M))
         # x = x + ff(norm3(x)); the FF output is only consumed by proj_out -> emitted 16-bit (sum formed in fp32)
         n = be.layernorm(tok, *T["ln3"], 1e-5, dt)
         g = self._linear(n, T["ff1"], M, out_dtype=dt, epilogue=L.EPI_GEGLU)
-        t = self._ff_out(g, T["ff2"], M, tok)
+        t = self._ff_out(g, T["ff2"], M, self._adapt(T, "ff", tok, M))
         return self._linear(t, P["pout"], M, residual=x, colstats=True, alg_k=d)
 
     def _temporal_tx(self, tt: _TemporalTransformerP, x, B, F, H, W):
@@ -776,7 +782,7 @@ class UNetSD_T2VBase(nn.Module):
         def attn2(n):
             return self_attn(self._linear(n, P["tb"]["qkv2"], M, out_dtype=dt))
 
-        t = self._tblock(P["tb"], tok, M, d, heads, self_attn, attn2)
+        t = self._tblock(P["tb"], tok, M, d, heads, self_attn, attn2, geom=(B, F, S))
         return self._linear(t, P["pout"], M, residual=x, colstats=True, alg_k=d)
 
     # -- forward -------------------------------------------------------------------------------
@@ -784,7 +790,8 @@ class UNetSD_T2VBase(nn.Module):
         """Everything ahead of the trunk for G kwarg sets evaluated on the same latent batch `shape` =
         (B, C, F, H, W): G*B units, unit index g*B + b.  Returns None when the sets cannot share one batch, else
         dict(extra=[G*B, C_extra, F, H, W] fp32 stem channels after the latent's (or None), ctx=[G*B (x F), L, D],
-        per_frame=bool, fps=[G*B] or None).  Only `x` and `t` change between the denoise steps of one prompt, so a
+        per_frame=bool, fps=[G*B] or None; optionally body={keyword of _body: tensor [G*B, ...] or a dict of such}: further
+        prompt constants of a subclass's `_body`, unit-major).  Only `x` and `t` change between the denoise steps of one prompt, so a
         sampling session evaluates this ONCE (vgen_amd/session.py)."""
         if any(kw.get("y") is None for kw in kwargs_list):
             return None
@@ -851,7 +858,7 @@ class UNetSD_T2VBase(nn.Module):
         if prep["extra"] is not None:
             xs = torch.cat([xs, prep["extra"]], 1)
         out = self._trunk(xs, t.repeat(G), prep["ctx"], prep["fps"], ctx_per_frame=prep["per_frame"],
-                          shared_groups=self.shared_prefix_groups(prep, G, x.shape[0]))
+                          shared_groups=self.shared_prefix_groups(prep, G, x.shape[0]), body_kw=prep.get("body"))
         return tuple(out.chunk(G, 0))
 
     @staticmethod
@@ -922,17 +929,18 @@ class UNetSD_T2VBase(nn.Module):
         ctx16 = be.act_cast(ctx.to(device=dev, dtype=torch.float32).reshape(nctx * Lctx, -1).contiguous(), 0, dt)
         return self._linear(ctx16, self._packed["kv_all"], nctx * Lctx, out_dtype=dt)
 
-    def _trunk(self, x, t, ctx, fps=None, ctx_per_frame=False, shared_groups=1):
+    def _trunk(self, x, t, ctx, fps=None, ctx_per_frame=False, shared_groups=1, body_kw=None):
         """Embeddings + encoder / middle / decoder / head on rows (unet_t2v.py:241-277).  `x` carries every
         input channel of the stem conv ([B, C, F, H, W]), `ctx` every cross-attention token: [B, L, 1024] shared
-        by the frames of a video, or [B * F, L, 1024] with ctx_per_frame (frame-major per prompt)."""
+        by the frames of a video, or [B * F, L, 1024] with ctx_per_frame (frame-major per prompt).  body_kw: a model's own
+        prompt constants for its `_body` (the optional "body" entry of _prepare_units; None for the t2v trunk)."""
         if self._packed is None:
             self.pack()
         B, C, F, H, W = x.shape
         assert ctx.shape[0] == (B * F if ctx_per_frame else B), (tuple(ctx.shape), B, F, ctx_per_frame)
         emb_all = self._embed(t, fps, B, x.device)
         kv_all = self._context_kv(ctx, x.device)
-        return self._body(x, emb_all, kv_all, ctx.shape[1], ctx_per_frame, shared_groups=shared_groups)
+        return self._body(x, emb_all, kv_all, ctx.shape[1], ctx_per_frame, shared_groups=shared_groups, **(body_kw or {}))
 
     def _body(self, x, emb_all, kv_all, Lctx, ctx_per_frame=False, out=None, shared_groups=1):
         """Stem conv, encoder / middle / decoder, head: rows in, [B, out_dim, F, H, W] fp32 out (into `out`).
