@@ -1,0 +1,242 @@
+"""Regression fixture of the weight PACKING and of the LAUNCH SEQUENCE of every tiny model fixture, recorded from a chosen
+commit of this repository (its sha goes into the file) so that a later host-side refactor can be held to "same packed bits,
+same launches" without trusting the code under test.  Only surface that is stable across commits is used: constructors,
+`load_state_dict`, `pack()`, `ops.set_backend`, `calibrate._named_packed`, `forward` / `forward_units` / `decode` / `encode`.
+
+Per case (a model fixture in one precision mode) the record is kept as sha256 sums, so that the file stays a few kB:
+  packed  the record of a weight is (`_named_packed` path, dtype, shape, sha256 of the bits, sha256 of the bits of `.vgen_dw`
+          or none) — elementwise roundings of seeded weights: host-independent.  Stored: the number of paths, the sha256 over
+          all records in order, and one short digest per top-level key of `_packed` (a block; names once per fixture under
+          "groups") so that a mismatch names the block;
+  traces  one `forward` and one `forward_units` cond / uncond pair (VAE: decode, encode) through a recording wrapper around
+          the ABI emulator.  The record of a launch is the op name plus, for every argument, its shape, dtype, strides,
+          storage offset, scalar value, dataclass fields, `.vgen_dw` / `.vgen_cs` presence; no float tensor contents.
+          Stored: the number of launches, the sha256 over all records in order, and one short digest per CHUNK consecutive
+          launches so that a mismatch names the stretch.
+Equal sums are equal records: nothing is left out of them.
+
+    python tests/golden/make_pack_trace.py     # rewrites tests/golden/pack_trace.json from the commit that is checked out
+"""
+from __future__ import annotations
+
+import dataclasses
+import hashlib
+import json
+import os
+import subprocess
+import sys
+import types
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from oracle import torch_ref  # noqa: E402
+from oracle.abi_emulator import EmuBackend  # noqa: E402
+
+UNET_TINY_MODES = ("fast", "mixed", "high", "mixed:e0d01", "mixed:e0d0:all", "mixed:e0d0:noextra", "mixed:e0m2d0t12")
+# the other families in the mode a config without `precision` gets: "mixed", "high" with spatial condition stems
+FAMILIES = ("unet_sr600_tiny", "unet_i2vgen_tiny", "unet_videolcm_tiny", "unet_tft2v_tiny", "unet_vcomposer_tiny",
+            "unet_histogram_tiny", "unet_dreamvideo_tiny")
+CASES = [f"unet_tiny/{p}" for p in UNET_TINY_MODES] + [f"{f}/default" for f in FAMILIES] + \
+    ["vae_tiny/fast", "vae_tiny/high"]
+CHUNK = 32
+
+
+def gold(name):
+    return torch.load(os.path.join(HERE, name), map_location="cpu", weights_only=False)
+
+
+def _sha(lines):
+    return hashlib.sha256("\n".join(lines).encode()).hexdigest()
+
+
+# -- the recording backend -----------------------------------------------------------------------------------------------
+class EmuAdapter(EmuBackend):
+    """the emulator plus vgen_adapter restated from the header (16-bit operands, fp32 accumulation, hidden activation
+    rounded once), as in tests/test_dreamvideo.py"""
+
+    def adapter(self, x, Wd, Wu, bu, hb, rows_per_hb, h, out=None):
+        dt = Wd.dtype
+        idx = torch.arange(x.shape[0]) // rows_per_hb
+        s = x.to(dt).float() @ Wd.float().t() + hb[idx]
+        g = (0.5 * s * (1.0 + torch.erf(s * 0.7071067811865476))).to(dt).float()
+        o = x + bu + g @ Wu.float().t()
+        if out is None:
+            return o
+        out.copy_(o)
+        return out
+
+
+def describe(v):
+    if torch.is_tensor(v):
+        return ["T", str(v.dtype), list(v.shape), list(v.stride()), int(v.storage_offset()),
+                getattr(v, "vgen_dw", None) is not None, getattr(v, "vgen_cs", None) is not None]
+    if dataclasses.is_dataclass(v) and not isinstance(v, type):
+        return {"@": type(v).__name__, **{f.name: describe(getattr(v, f.name)) for f in dataclasses.fields(v)}}
+    if isinstance(v, dict):
+        return {str(k): describe(v[k]) for k in sorted(v, key=str)}
+    if isinstance(v, (tuple, list)):
+        return [describe(e) for e in v]
+    if isinstance(v, float):
+        return repr(v)
+    if v is None or isinstance(v, (bool, int, str)):
+        return v
+    if isinstance(v, torch.dtype):
+        return str(v)
+    return f"<{type(v).__name__}>"
+
+
+class Recorder:
+    """every call the model makes on the backend, in order; the emulator's calls on itself are not launches"""
+
+    def __init__(self, inner):
+        self._inner, self.calls = inner, []
+
+    def __getattr__(self, name):
+        attr = getattr(self._inner, name)
+        if not callable(attr):
+            return attr
+
+        def call(*a, **k):
+            self.calls.append([name, describe(a), describe(k)])
+            return attr(*a, **k)
+        return call
+
+    def take(self):
+        calls, self.calls = self.calls, []
+        text = [json.dumps(c, sort_keys=True, separators=(",", ":")) for c in calls]
+        return {"n": len(text), "sha256": _sha(text), "chunks": [_sha(text[i: i + CHUNK])[:10] for i in range(0, len(text), CHUNK)]}
+
+
+# -- the cases -----------------------------------------------------------------------------------------------------------
+def _bits(t):
+    t = t.detach().contiguous().cpu()
+    raw = t.view(torch.int16) if t.element_size() == 2 else t.view(torch.int32) if t.element_size() == 4 else t
+    return hashlib.sha256(raw.numpy().tobytes()).hexdigest()
+
+
+def packed_record(model):
+    """-> (top-level keys of `_packed` that hold tensors, one digest per key, number of paths, sha256 over all records)"""
+    from vgen_amd.calibrate import _named_packed
+    text, groups = [], {}
+    for path, w in _named_packed(model):
+        dw = getattr(w, "vgen_dw", None) if w.element_size() == 2 else None
+        text.append(f"{path} {w.dtype} {list(w.shape)} {_bits(w)} {None if dw is None else _bits(dw)}")
+        groups.setdefault(path.split("/")[0], []).append(text[-1])
+    return list(groups), [_sha(v)[:10] for v in groups.values()], len(text), _sha(text)
+
+
+def _build(case):
+    """-> (model, forward kwargs, the two kwarg sets of the pair or None, (x, t))"""
+    fixture, mode = case.split("/", 1)
+    prec = {} if mode == "default" else {"precision": mode}
+    g = gold(fixture + ".pt")
+    ns = lambda comps, res: types.SimpleNamespace(video_compositions=comps, resolution=res)
+    if fixture == "unet_dreamvideo_tiny":
+        from vgen_amd.synth import seeded_state_dict
+        from vgen_amd.unet_dreamvideo import UNetSD_DreamVideo
+        m = UNetSD_DreamVideo(**g["cfg"], compute_dtype="fp16", **prec).eval()
+        m.load_state_dict(seeded_state_dict(g["shapes"], seed=g["seed"], recipe=g["recipe"]), strict=True)
+        B, C, F, H, W = g["latent"]                      # the inputs of tests/golden/make_dreamvideo_golden.py::inputs
+        gen = torch.Generator("cpu").manual_seed(g["input_seed"])
+        x = torch.randn(B, C, F, H, W, generator=gen)
+        y = torch.randn(B, g["ctx"], 1024, generator=gen)
+        one = torch.randn(B, 1, 1024, generator=gen)
+        kw = dict(y=y, y_image=one, ag_strength=1.0)
+        kw2 = dict(y=torch.zeros_like(y), y_image=torch.zeros_like(one), ag_strength=1.0)
+        return m, kw, [kw, kw2], (x, torch.full((B,), g["t"], dtype=torch.long))
+    sd = torch_ref.synth_state_dict(g["shapes"], seed=g["seed"])
+    if fixture == "vae_tiny":
+        from vgen_amd.vae import AutoencoderKL
+        m = AutoencoderKL(ddconfig=g["ddconfig"], embed_dim=4, compute_dtype="fp16", **prec).eval()
+        m.load_state_dict(sd, strict=True)
+        return m, None, None, None
+    from vgen_amd.unet import UNetSD_SR600, UNetSD_T2VBase
+    from vgen_amd.unet_i2vgen import UNetSD_I2VGen
+    from vgen_amd.unet_videolcm import UNetSD_TFT2V, UNetSD_VideoLCM
+    roll = torch.roll(g["y"], 1, 1)
+    if fixture == "unet_tiny":
+        m, kw, kw2 = UNetSD_T2VBase(**g["cfg"], compute_dtype="fp16", **prec), dict(y=g["y"]), dict(y=torch.roll(g["y"], 1, 0))
+    elif fixture == "unet_sr600_tiny":
+        m, kw, kw2 = UNetSD_SR600(**g["cfg"], compute_dtype="fp16", **prec), dict(y=g["y"]), dict(y=torch.zeros_like(g["y"]))
+    elif fixture == "unet_i2vgen_tiny":
+        m = UNetSD_I2VGen(**g["cfg"], compute_dtype="fp16", **prec)
+        kw = dict(y=g["y"], image=g["image"], local_image=g["local_image"], fps=g["fps"])
+        kw2 = dict(kw, y=roll)
+    elif fixture == "unet_videolcm_tiny":
+        m = UNetSD_VideoLCM(config=ns(["text"], [64, 128]), **g["cfg"], compute_dtype="fp16", **prec)
+        kw, kw2 = dict(y=g["y"]), dict(y=roll)
+    elif fixture == "unet_tft2v_tiny":
+        m = UNetSD_TFT2V(config=ns(["text", "image"], [64, 128]), **g["cfg"], compute_dtype="fp16", **prec)
+        kw, kw2 = dict(y=g["y"], image=g["image"]), dict(y=roll, image=g["image"] * 0.5)
+    elif fixture == "unet_vcomposer_tiny":
+        m = UNetSD_TFT2V(config=ns(g["comps"], g["resolution"]), **g["cfg"], compute_dtype="fp16", **prec)
+        conds = {k: v.float() for k, v in g["conds"].items()}
+        kw = dict(y=g["y"], image=g["image"], **conds)
+        kw2 = dict(kw, y=roll, depth=conds["depth"] * 0.5)
+    elif fixture == "unet_histogram_tiny":
+        m = UNetSD_VideoLCM(config=ns(g["comps"], g["resolution"]), **g["cfg"], compute_dtype="fp16", **prec)
+        canny = g["canny"].float()
+        kw = dict(y=g["y"], histogram=g["histogram"], canny=canny)
+        kw2 = dict(y=roll, histogram=g["histogram"] * 0.5, canny=canny)
+    else:
+        raise KeyError(case)
+    m = m.eval()
+    m.load_state_dict(sd, strict=True)
+    return m, kw, [kw, kw2], (g["x"], g["t"])
+
+
+@torch.no_grad()
+def record(case):
+    """{"precision": the resolved mode, "groups": [...], "packed": {"n", "sha256", "groups": [...]}, "traces": {name: {"n",
+    "sha256", "chunks": [...]}}} of one case"""
+    from vgen_amd import ops
+    rec = Recorder(EmuAdapter())
+    prev = ops.set_backend(rec)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        m, kw, pair, xt = _build(case)
+        m.pack()
+        names, digests, n, whole = packed_record(m)
+        out = {"precision": m.precision, "groups": names, "packed": {"n": n, "sha256": whole, "groups": digests}, "traces": {}}
+        rec.take()
+        if case.startswith("vae_tiny"):
+            g = gold("vae_tiny.pt")
+            m.decode(g["z"])
+            out["traces"]["decode"] = rec.take()
+            m.encode(g["img"])
+            out["traces"]["encode"] = rec.take()
+        else:
+            m(*xt, **kw)
+            out["traces"]["forward"] = rec.take()
+            m.forward_units(*xt, pair)
+            out["traces"]["forward_units"] = rec.take()
+        return out
+    finally:
+        torch.set_num_threads(threads)
+        ops.set_backend(prev)
+
+
+def main():
+    sha = subprocess.run(["git", "rev-parse", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
+    dirty = subprocess.run(["git", "status", "--porcelain", "--", "vgen_amd", "oracle"], cwd=ROOT, capture_output=True,
+                           text=True, check=True).stdout.strip()
+    assert not dirty, f"record from a clean checkout:\n{dirty}"
+    res = {"recorded_from": sha, "groups": {}, "cases": {}}
+    for case in CASES:
+        r = record(case)
+        assert res["groups"].setdefault(case.split("/")[0], r["groups"]) == r.pop("groups"), case  # a fixture's modes: one structure
+        res["cases"][case] = r
+        print(case, r["precision"], r["packed"]["n"], {k: v["n"] for k, v in r["traces"].items()}, flush=True)
+    with open(os.path.join(HERE, "pack_trace.json"), "w") as f:            # one case per line
+        line = lambda d: ",\n".join(f"{json.dumps(k)}:{json.dumps(v, separators=(',', ':'))}" for k, v in d.items())
+        f.write('{"recorded_from":"%s","groups":{\n%s\n},"cases":{\n%s\n}}\n' % (sha, line(res["groups"]), line(res["cases"])))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,47 @@
+"""CPU: weight packing and launch sequence of every tiny fixture against a record taken from an EARLIER commit of this
+repository (tests/golden/pack_trace.json, written by tests/golden/make_pack_trace.py in a checkout of the commit named in its
+"recorded_from") — which weights are two-term, their exact bits, the order and keys of `_packed`, and every backend call of
+a forward / a forward_units pair with all its shapes, strides, scalars and operand forms.  Host-side rework of the packers,
+the precision rule or the block bodies must leave all of it as it was; a change that is MEANT to alter it regenerates the file."""
+import importlib.util
+import json
+import os
+
+import pytest
+
+from conftest import GOLD
+
+
+def _gen():
+    spec = importlib.util.spec_from_file_location("make_pack_trace", os.path.join(GOLD, "make_pack_trace.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+GEN = _gen()
+with open(os.path.join(GOLD, "pack_trace.json")) as _f:
+    WANT = json.load(_f)
+
+
+def test_the_record_covers_every_case_and_names_its_commit():
+    assert list(WANT["cases"]) == GEN.CASES and len(GEN.CASES) == 16
+    assert len(WANT["recorded_from"]) == 40 and int(WANT["recorded_from"], 16) >= 0
+    assert set(WANT["groups"]) == {c.split("/")[0] for c in GEN.CASES}
+
+
+@pytest.mark.parametrize("case", GEN.CASES)
+def test_packed_operands_and_launch_trace_equal_the_recorded_commit(case):
+    want, got = WANT["cases"][case], GEN.record(case)
+    assert got["precision"] == want["precision"]
+    names = WANT["groups"][case.split("/")[0]]
+    assert got["groups"] == names                                        # top-level keys and insertion order of `_packed`
+    moved = [k for k, a, b in zip(names, got["packed"]["groups"], want["packed"]["groups"]) if a != b]
+    assert not moved, (len(moved), moved[:8])                            # the blocks whose paths, dtypes, shapes or bits moved
+    assert got["packed"] == want["packed"]                               # every path, dtype, shape, bit and two-term form
+    assert list(got["traces"]) == list(want["traces"])
+    for name, w in want["traces"].items():
+        g = got["traces"][name]
+        first = next((i for i, (a, b) in enumerate(zip(g["chunks"], w["chunks"])) if a != b), None)
+        assert first is None, f"{name}: launches {first * GEN.CHUNK}..{first * GEN.CHUNK + GEN.CHUNK - 1} differ"
+        assert g == w, name                                               # every launch with all its arguments, in order

@@ -143,60 +143,49 @@ class _UpP(nn.Module):
 # ------------------------------------------------------------------------------------------
 # weight packing helpers (fp32 parameters -> 16-bit tap-GEMM operands)
 # ------------------------------------------------------------------------------------------
-_SPLIT_WEIGHTS = False     # set by pack() of a model built with precision="high" (ops.split_weight)
-
-
-class split_weights:
-    """`with split_weights(model.precision == "high"):` around a pack(): the packers below then keep every operand's
-    rounding residual (high-precision mode of the UNets and the VAE)."""
-
-    def __init__(self, on):
-        self.on = bool(on)
-
-    def __enter__(self):
-        global _SPLIT_WEIGHTS
-        self.prev, _SPLIT_WEIGHTS = _SPLIT_WEIGHTS, self.on
-
-    def __exit__(self, *exc):
-        global _SPLIT_WEIGHTS
-        _SPLIT_WEIGHTS = self.prev
-
-
-def _w16(p32: torch.Tensor, dt) -> torch.Tensor:
-    """packed fp32 [N, K] -> the 16-bit tap-GEMM operand (+ its rounding residual in high-precision mode)"""
-    if _SPLIT_WEIGHTS:
+def _w16(p32: torch.Tensor, dt, split: bool) -> torch.Tensor:
+    """packed fp32 [N, K] -> the 16-bit tap-GEMM operand; split: two-term, i.e. with its rounding residual [W_hi | W_lo]
+    attached (ops.split_weight).  Every packer below takes `split` from its caller: a model's precision policy
+    (UNetSD_T2VBase._two_term, AutoencoderKL._pack) decides it per weight, nothing here reads state."""
+    if split:
         return ops.split_weight(p32.float(), dt)
     return p32.to(dt).contiguous()
 
 
-def _w16_cat(parts, dt) -> torch.Tensor:
+def _w16_cat(parts, dt, split: bool) -> torch.Tensor:
     """column-concatenated operand (ResBlock out-conv + its 1x1 skip conv as a second K segment)"""
-    return _w16(torch.cat([p.float() for p in parts], 1), dt)
+    return _w16(torch.cat([p.float() for p in parts], 1), dt, split)
 
 
-def pack_conv3x3(w: torch.Tensor, dt=None) -> torch.Tensor:
-    """[Cout, Cin, 3, 3] -> [Cout, 9*Cin], column (ky*3+kx)*Cin + c (fp32 when dt is None)."""
-    p = w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1)
-    return p if dt is None else _w16(p, dt)
+def rows_conv3x3(w: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> [Cout, 9*Cin], column (ky*3+kx)*Cin + c (the parameter's own dtype: a part for _w16_cat)."""
+    return w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1)
 
 
-def pack_temporal(w: torch.Tensor, dt) -> torch.Tensor:
+def rows_linear(w: torch.Tensor) -> torch.Tensor:
+    return w.detach().reshape(w.shape[0], -1)
+
+
+def pack_conv3x3(w: torch.Tensor, dt, split: bool) -> torch.Tensor:
+    return _w16(rows_conv3x3(w), dt, split)
+
+
+def pack_temporal(w: torch.Tensor, dt, split: bool) -> torch.Tensor:
     """[Cout, Cin, 3, 1, 1] -> [Cout, 3*Cin], column kt*Cin + c."""
-    return _w16(w.detach()[:, :, :, 0, 0].permute(0, 2, 1).reshape(w.shape[0], -1), dt)
+    return _w16(w.detach()[:, :, :, 0, 0].permute(0, 2, 1).reshape(w.shape[0], -1), dt, split)
 
 
-def pack_linear(w: torch.Tensor, dt=None) -> torch.Tensor:
-    p = w.detach().reshape(w.shape[0], -1)
-    return p if dt is None else _w16(p, dt)
+def pack_linear(w: torch.Tensor, dt, split: bool) -> torch.Tensor:
+    return _w16(rows_linear(w), dt, split)
 
 
-def pack_geglu(w: torch.Tensor, b: torch.Tensor, dt):
+def pack_geglu(w: torch.Tensor, b: torch.Tensor, dt, split: bool):
     """GEGLU.proj rows [value(0..I) | gate(I..2I)] -> interleaved [16 value | 16 gate] blocks."""
     inner = w.shape[0] // 2
     assert inner % 16 == 0
     idx = torch.arange(inner, device=w.device).view(-1, 16)
     perm = torch.cat([idx, idx + inner], dim=1).reshape(-1)
-    return _w16(w.detach()[perm], dt), b.detach()[perm].float().contiguous()
+    return _w16(w.detach()[perm], dt, split), b.detach()[perm].float().contiguous()
 
 
 def pack_small_conv3x3(w: torch.Tensor, kpad: int, dt, split: bool = False) -> torch.Tensor:
@@ -215,6 +204,66 @@ def pack_small_conv3x3(w: torch.Tensor, kpad: int, dt, split: bool = False) -> t
 
 def _f32(t):
     return t.detach().float().contiguous()
+
+
+def resolve_precision(precision, calibration):
+    """The `precision` / `calibration` constructor keywords of the UNets -> (mode, tables, calibration, auto): the resolved
+    mode "fast" | "high" | "mixed" | "calibrated", the UNetSD_T2VBase.MIXED_* tables a "mixed:<spec>" replaces ({} otherwise),
+    the calibration file (or None) and the `calibration: auto` setting (None | True | the path to save to / load from)."""
+    # "fast": one 16-bit operand pair per GEMM (the reference's autocast arithmetic; 1.33e-3 from its fp32 forward);
+    # "high": every packed weight also carries its 16-bit rounding residual (one dual-W launch per layer: A . (W_hi +
+    # W_lo)^T) and the two plain residual-stream casts that feed GEMMs are two-term: 6.9e-4, ~1.35x the step time;
+    # "mixed" (default): the same, with two-term weights only at the full-resolution level: 8.3e-4 at ~1.1x
+    # (DESIGN §4.1); set before the first forward / pack().
+    # What "meets 1e-3" rests on (ADVICE r03): seeded SYNTHETIC weights — pretrained checkpoints are not available
+    # offline — on the full-width models (ABI emulator; GPU numbers of the rules that ran there in DESIGN §4.1): t2v
+    # 7.7e-4 / 7.6e-4 (t = 501) / 6.5e-4 (Student-t weights), I2VGen 8.8e-4, VideoLCM / TFT2V / SR600 7.5 - 7.9e-4.  It is a property of those trunks,
+    # not of the mode: on the 3-level dim-64 test model the level rule gives 1.1e-3 and even "high" only 9.2e-4
+    # (what is left there is activation rounding), and the vcomposer composition list at 32 frames 896 x 512
+    # (BASELINE config 5, stage 1) measures 1.01e-3 in "mixed", 8.6e-4 in "high" — use "high" there.  A drop-in user pays ~1.1x the single-pass step and
+    # the [W_hi | W_lo] copies of the level-0 weights (~0.3 GB) for it; precision="fast" is the reference's own
+    # arithmetic (1.33e-3 where its autocast forward lands at 2.10e-3).
+    mode, tables = precision or "mixed", {}
+    if mode.startswith("mixed:"):
+        # "mixed:e0d01": two-term weights in encoder level 0 and decoder levels 0, 1 ("m3": the middle block at level 3);
+        # a trailing ":all" also keeps the FeedForward / cross-attention-query weights two-term (MIXED_SINGLE_KINDS)
+        # and drops the per-kind additions of MIXED_EXTRA_KINDS (= the r03 rule); ":noextra" drops only the latter
+        import re
+        spec = mode.split(":", 1)[1]
+        if spec.endswith(":all") or spec == "all":
+            tables.update(MIXED_SINGLE_KINDS=(), MIXED_EXTRA_KINDS={})
+            spec = spec[:-4] if spec.endswith(":all") else "e0d0"
+        elif spec.endswith(":noextra") or spec == "noextra":      # the level rule minus MIXED_SINGLE_KINDS only
+            tables.update(MIXED_EXTRA_KINDS={})                   # (the rule r04's last GPU call measured)
+            spec = spec[:-8] if spec.endswith(":noextra") else "e0d0"
+        assert re.fullmatch(r"(?:[edmt]\d*)*", spec), f"precision={mode!r}"
+        lv = {"e": (), "d": (), "m": (), "t": ()}
+        for side, digits in re.findall(r"([edmt])(\d*)", spec):
+            lv[side] = tuple(int(c) for c in digits)
+        tables["MIXED_LEVELS"] = {"enc": lv["e"], "mid": lv["m"], "dec": lv["d"], "tx": lv["t"]}
+        mode = "mixed"
+    # "calibrated" (r05/r06, vgen_amd/calibrate.py): every weight ONE 16-bit matrix whose rounding was chosen by error
+    # feedback from a calibration batch.  Either reached in place (build "high", calibrate_single_pass) or from a file
+    # such a pass wrote (save_calibrated): `precision="calibrated", calibration=<path>` — pack() rounds to nearest in the
+    # calibrated structure and load_calibrated() overwrites the matrices, so a config can name the mode:
+    #   UNet: {type: UNetSD_T2VBase, ..., precision: calibrated, calibration: t2v_fp16.cal}
+    # r06: `calibration: auto` (or `auto:<path>`) — the headline mode as a yaml-only switch.  The model packs two-term and
+    # calibrates ITSELF once, at its first evaluation, on calibrate.calibration_batch at the shapes of that call (seeded
+    # noise / prompts at timesteps spread over the schedule; the call's other conditioning tensors repeated) — before any
+    # sampling session captures a graph.  With a path the result is saved there (and loaded instead when the file
+    # already exists), so only the first run of a deployment pays the ~85 s pass.  See _maybe_auto_calibrate.
+    auto = None
+    if isinstance(calibration, str) and (calibration == "auto" or calibration.startswith("auto:")):
+        if mode != "calibrated":
+            raise ValueError("calibration='auto' is only meaningful with precision='calibrated'")
+        auto, calibration, mode = calibration[5:] or True, None, "high"
+    if mode == "calibrated" and not calibration:
+        raise ValueError("precision='calibrated' needs calibration=<file written by vgen_amd.calibrate.save_calibrated>; "
+                         "to calibrate a model, build it with precision='high' and call calibrate_single_pass")
+    if calibration and mode != "calibrated":
+        raise ValueError(f"calibration={calibration!r} is only meaningful with precision='calibrated'")
+    assert mode in ("fast", "high", "mixed", "calibrated")
+    return mode, tables, calibration, auto
 
 
 # ------------------------------------------------------------------------------------------
@@ -251,63 +300,10 @@ class UNetSD_T2VBase(nn.Module):
         self.attn_scales = list(attn_scales)
         self.use_fps_condition = use_fps_condition
         self.compute_dtype = ops.sixteen(compute_dtype)
-        # "fast": one 16-bit operand pair per GEMM (the reference's autocast arithmetic; 1.33e-3 from its fp32 forward);
-        # "high": every packed weight also carries its 16-bit rounding residual (one dual-W launch per layer: A . (W_hi +
-        # W_lo)^T) and the two plain residual-stream casts that feed GEMMs are two-term: 6.9e-4, ~1.35x the step time;
-        # "mixed" (default): the same, with two-term weights only at the full-resolution level: 8.3e-4 at ~1.1x
-        # (DESIGN §4.1); set before the first forward / pack().
-        # What "meets 1e-3" rests on: seeded SYNTHETIC weights — pretrained checkpoints are not available
-        # offline — on the full-width models (ABI emulator; GPU numbers of the rules that ran there in DESIGN §4.1): t2v
-        # 7.7e-4 / 7.6e-4 (t = 501) / 6.5e-4 (Student-t weights), I2VGen 8.8e-4, VideoLCM / TFT2V / SR600 7.5 - 7.9e-4.  It is a property of those trunks,
-        # not of the mode: on the 3-level dim-64 test model the level rule gives 1.1e-3 and even "high" only 9.2e-4
-        # (what is left there is activation rounding), and the vcomposer composition list at 32 frames 896 x 512
-        # (BASELINE config 5, stage 1) measures 1.01e-3 in "mixed", 8.6e-4 in "high" — use "high" there.  A drop-in user pays ~1.1x the single-pass step and
-        # the [W_hi | W_lo] copies of the level-0 weights (~0.3 GB) for it; precision="fast" is the reference's own
-        # arithmetic (1.33e-3 where its autocast forward lands at 2.10e-3).
-        self.precision = precision or "mixed"
-        if self.precision.startswith("mixed:"):
-            # "mixed:e0d01": two-term weights in encoder level 0 and decoder levels 0, 1 ("m3": the middle block at level 3);
-            # a trailing ":all" also keeps the FeedForward / cross-attention-query weights two-term (MIXED_SINGLE_KINDS)
-            # and drops the per-kind additions of MIXED_EXTRA_KINDS (= the r03 rule); ":noextra" drops only the latter
-            import re
-            spec = self.precision.split(":", 1)[1]
-            if spec.endswith(":all") or spec == "all":
-                self.MIXED_SINGLE_KINDS, self.MIXED_EXTRA_KINDS = (), {}
-                spec = spec[:-4] if spec.endswith(":all") else "e0d0"
-            elif spec.endswith(":noextra") or spec == "noextra":      # the level rule minus MIXED_SINGLE_KINDS only
-                self.MIXED_EXTRA_KINDS = {}                          # (the rule r04's last GPU call measured)
-                spec = spec[:-8] if spec.endswith(":noextra") else "e0d0"
-            assert re.fullmatch(r"(?:[edmt]\d*)*", spec), f"precision={self.precision!r}"
-            lv = {"e": (), "d": (), "m": (), "t": ()}
-            for side, digits in re.findall(r"([edmt])(\d*)", spec):
-                lv[side] = tuple(int(c) for c in digits)
-            self.MIXED_LEVELS = {"enc": lv["e"], "mid": lv["m"], "dec": lv["d"], "tx": lv["t"]}
-            self.precision = "mixed"
-        # "calibrated" (r05/r06, vgen_amd/calibrate.py): every weight ONE 16-bit matrix whose rounding was chosen by error
-        # feedback from a calibration batch.  Either reached in place (build "high", calibrate_single_pass) or from a file
-        # such a pass wrote (save_calibrated): `precision="calibrated", calibration=<path>` — pack() rounds to nearest in the
-        # calibrated structure and load_calibrated() overwrites the matrices, so a config can name the mode:
-        #   UNet: {type: UNetSD_T2VBase, ..., precision: calibrated, calibration: t2v_fp16.cal}
-        self.calibration = kwargs.pop("calibration", None)
-        # r06: `calibration: auto` (or `auto:<path>`) — the headline mode as a yaml-only switch.  The model packs two-term and
-        # calibrates ITSELF once, at its first evaluation, on calibrate.calibration_batch at the shapes of that call (seeded
-        # noise / prompts at timesteps spread over the schedule; the call's other conditioning tensors repeated) — before any
-        # sampling session captures a graph.  With a path the result is saved there (and loaded instead when the file
-        # already exists), so only the first run of a deployment pays the ~85 s pass.  See _maybe_auto_calibrate.
-        self._auto_cal_cfg = self._auto_cal = None
-        if isinstance(self.calibration, str) and (self.calibration == "auto" or self.calibration.startswith("auto:")):
-            if self.precision != "calibrated":
-                raise ValueError("calibration='auto' is only meaningful with precision='calibrated'")
-            self._auto_cal_cfg = self.calibration[5:] or True
-            self._auto_cal = self._auto_cal_cfg
-            self.calibration = None
-            self.precision = "high"
-        if self.precision == "calibrated" and not self.calibration:
-            raise ValueError("precision='calibrated' needs calibration=<file written by vgen_amd.calibrate.save_calibrated>; "
-                             "to calibrate a model, build it with precision='high' and call calibrate_single_pass")
-        if self.calibration and self.precision != "calibrated":
-            raise ValueError(f"calibration={self.calibration!r} is only meaningful with precision='calibrated'")
-        assert self.precision in ("fast", "high", "mixed", "calibrated")
+        mode, tables, self.calibration, self._auto_cal_cfg = resolve_precision(precision, kwargs.pop("calibration", None))
+        self.precision, self._auto_cal = mode, self._auto_cal_cfg
+        for k, v in tables.items():                 # a "mixed:<spec>" replaces the class-level MIXED_* tables on this model
+            setattr(self, k, v)
         # two-term ACTIVATIONS at the two places where a plain fp32 -> 16-bit cast of a residual-stream tensor is a GEMM
         # operand (attribution, DESIGN §4.1: 0.157 + 0.126 of the 0.758e-6 error energy left once the weights are exact):
         # the raw input of the ResBlock's 1x1 skip conv and the token stream entering proj_out.  On in every mode but
@@ -365,6 +361,7 @@ class UNetSD_T2VBase(nn.Module):
         self.out = _seq(nn.GroupNorm(32, cout), None, nn.Conv2d(cout, self.out_dim, 3, padding=1))
         nn.init.zeros_(self.out[-1].weight)
 
+        self._levels = self._block_levels()
         self._packed = None
         self._epoch = 0            # bumped whenever the parameters may have changed (sessions / caches key on it)
 
@@ -410,8 +407,7 @@ class UNetSD_T2VBase(nn.Module):
     @torch.no_grad()
     def pack(self, device=None):
         """Build the 16-bit tap-GEMM operands (once per weight load)."""
-        with split_weights(self.precision == "high"):
-            P = self._pack(device)
+        P = self._pack(device)
         if self.precision == "calibrated":
             from .calibrate import load_calibrated
             load_calibrated(self, self.calibration)
@@ -467,41 +463,23 @@ class UNetSD_T2VBase(nn.Module):
                 idx += 1
         return lv
 
-    def _wants_split(self, name):
-        if self.precision == "high":
-            return True
+    def _two_term(self, name, kind):
+        """Is weight `kind` of module `name` packed two-term ([W_hi | W_lo])?  `name`: a packed module's path, or "kv_all" /
+        "out" for the context K/V projection and the head conv (their kind is not looked at); kind: "conv1" | "conv2" |
+        "tconv" | "resample" | "pin" | "pout" | "qkv" | "o" | "q2" | "ff1" | "ff2".  A pure function of precision, the
+        MIXED_* tables (read at pack time: they may be assigned on a model) and the block -> level map."""
         if self.precision != "mixed":
-            return False
-        if name in ("kv_all", "out"):                                    # context K/V projection, head conv: full resolution
-            return 0 in self.MIXED_LEVELS["enc"] or 0 in self.MIXED_LEVELS["dec"]
+            return self.precision == "high"
+        levels = self.MIXED_LEVELS
+        if name in ("kv_all", "out"):                                    # they work at full resolution
+            return 0 in levels["enc"] or 0 in levels["dec"]
         parts = name.split(".")
-        top = parts[0] if parts[0] == "middle_block" else ".".join(parts[:2])
-        side, level = self._block_levels().get(top, (None, None))
-        if side is None:
-            return False
-        if level in self.MIXED_LEVELS[side]:
-            return True
-        if side in ("enc", "dec") and self.MIXED_EXTRA_KINDS.get(level):
-            return True                                                   # some kinds only: _kind_on() filters at the pack sites
-        if level in self.MIXED_LEVELS.get("tx", ()):
-            try:
-                return isinstance(self.get_submodule(name), (_SpatialTransformerP, _TemporalTransformerP))
-            except AttributeError:
-                return False
-        return False
-
-    def _kind_on(self, name, kind):
-        """Is weight `kind` of module `name` two-term?  (Called inside `with split_weights(self._wants_split(name))`.)"""
-        if not _SPLIT_WEIGHTS or self.precision != "mixed":
-            return _SPLIT_WEIGHTS
+        side, level = self._levels[parts[0] if parts[0] == "middle_block" else ".".join(parts[:2])]
         if kind in self.MIXED_SINGLE_KINDS:
             return False
-        parts = name.split(".")
-        top = parts[0] if parts[0] == "middle_block" else ".".join(parts[:2])
-        side, level = self._block_levels().get(top, (None, None))
-        if side is None or level in self.MIXED_LEVELS[side]:
+        if level in levels[side]:
             return True
-        if level in self.MIXED_LEVELS.get("tx", ()) and kind in ("qkv", "o", "pin", "pout"):
+        if level in levels.get("tx", ()) and kind in ("qkv", "o", "pin", "pout"):
             return True
         return side in ("enc", "dec") and kind in self.MIXED_EXTRA_KINDS.get(level, ())
 
@@ -532,15 +510,14 @@ class UNetSD_T2VBase(nn.Module):
             ws += [a2.to_k.weight, a2.to_v.weight]
             st._kv_off = off
             off += 2 * st.inner
-        with split_weights(self._wants_split("kv_all")):
-            P["kv_all"] = pack_linear(torch.cat(ws, 0), dt)
+        P["kv_all"] = pack_linear(torch.cat(ws, 0), dt, self._two_term("kv_all", "kv"))
         P["kv_width"] = off
 
         conv_in = self.input_blocks[0][0]
         cin0 = self._stem_channels()
         self._kpad_in = ((27 * cin0 + 63) // 64) * 64          # split stem: [hi | lo | hi] segments
         if cin0 % 64 == 0:
-            P["conv_in"] = (pack_conv3x3(conv_in.weight, dt), _f32(conv_in.bias))
+            P["conv_in"] = (pack_conv3x3(conv_in.weight, dt, self.precision == "high"), _f32(conv_in.bias))
         else:
             if cin0 > 16:
                 raise NotImplementedError("stem conv input channels must be <= 16 or a multiple of 64")
@@ -548,85 +525,68 @@ class UNetSD_T2VBase(nn.Module):
 
         def pack_res(rb: _ResBlockP, name):
             d = {}
-            on = lambda kind: split_weights(self._kind_on(name, kind))
+            on = lambda kind: self._two_term(name, kind)
             d["gn1"] = (_f32(rb.in_layers[0].weight), _f32(rb.in_layers[0].bias))
-            with on("conv1"):
-                d["conv1"] = (pack_conv3x3(rb.in_layers[2].weight, dt), _f32(rb.in_layers[2].bias))
+            d["conv1"] = (pack_conv3x3(rb.in_layers[2].weight, dt, on("conv1")), _f32(rb.in_layers[2].bias))
             d["gn2"] = (_f32(rb.out_layers[0].weight), _f32(rb.out_layers[0].bias))
             b2 = _f32(rb.out_layers[3].bias)
-            with on("conv2"):
-                if isinstance(rb.skip_connection, nn.Conv2d):
-                    wsk = pack_linear(rb.skip_connection.weight)
-                    # two-term skip operand [raw_hi | raw_lo]: the 1x1 weight appears twice
-                    w2 = _w16_cat([pack_conv3x3(rb.out_layers[3].weight), wsk] + ([wsk] if self._asplit else []), dt)
-                    b2 = (b2 + _f32(rb.skip_connection.bias)).contiguous()
-                else:
-                    w2 = pack_conv3x3(rb.out_layers[3].weight, dt)
+            if isinstance(rb.skip_connection, nn.Conv2d):
+                wsk = rows_linear(rb.skip_connection.weight)
+                # two-term skip operand [raw_hi | raw_lo]: the 1x1 weight appears twice
+                w2 = _w16_cat([rows_conv3x3(rb.out_layers[3].weight), wsk] + ([wsk] if self._asplit else []), dt, on("conv2"))
+                b2 = (b2 + _f32(rb.skip_connection.bias)).contiguous()
+            else:
+                w2 = pack_conv3x3(rb.out_layers[3].weight, dt, on("conv2"))
             d["conv2"] = (w2, b2)
             tc = rb.temopral_conv
-            with on("tconv"):
-                for i in (1, 2, 3, 4):
-                    sq = getattr(tc, f"conv{i}")
-                    d[f"tgn{i}"] = (_f32(sq[0].weight), _f32(sq[0].bias))
-                    d[f"tconv{i}"] = (pack_temporal(sq[-1].weight, dt), _f32(sq[-1].bias))
+            for i in (1, 2, 3, 4):
+                sq = getattr(tc, f"conv{i}")
+                d[f"tgn{i}"] = (_f32(sq[0].weight), _f32(sq[0].bias))
+                d[f"tconv{i}"] = (pack_temporal(sq[-1].weight, dt, on("tconv")), _f32(sq[-1].bias))
             return d
 
         def pack_tblock(tb: _TBlockP, cross: bool, name):
             d = {}
-            keep = lambda kind: split_weights(self._kind_on(name, kind))
+            on = lambda kind: self._two_term(name, kind)
             for i in (1, 2, 3):
                 n = getattr(tb, f"norm{i}")
                 d[f"ln{i}"] = (_f32(n.weight), _f32(n.bias))
-            a1 = tb.attn1
-            with keep("qkv"):
-                d["qkv1"] = pack_linear(torch.cat([a1.to_q.weight, a1.to_k.weight, a1.to_v.weight], 0), dt)
-            with keep("o"):
-                d["o1"] = (pack_linear(a1.to_out[0].weight, dt), _f32(a1.to_out[0].bias))
-            a2 = tb.attn2
+            a1, a2 = tb.attn1, tb.attn2
+            d["qkv1"] = pack_linear(torch.cat([a1.to_q.weight, a1.to_k.weight, a1.to_v.weight], 0), dt, on("qkv"))
+            d["o1"] = (pack_linear(a1.to_out[0].weight, dt, on("o")), _f32(a1.to_out[0].bias))
             if cross:
-                with keep("q2"):
-                    d["q2"] = pack_linear(a2.to_q.weight, dt)
+                d["q2"] = pack_linear(a2.to_q.weight, dt, on("q2"))
             else:
-                with keep("qkv"):
-                    d["qkv2"] = pack_linear(torch.cat([a2.to_q.weight, a2.to_k.weight, a2.to_v.weight], 0), dt)
-            with keep("o"):
-                d["o2"] = (pack_linear(a2.to_out[0].weight, dt), _f32(a2.to_out[0].bias))
-            with keep("ff1"):
-                d["ff1"] = pack_geglu(tb.ff.net[0].proj.weight, tb.ff.net[0].proj.bias, dt)
-            with keep("ff2"):
-                d["ff2"] = (pack_linear(tb.ff.net[2].weight, dt), _f32(tb.ff.net[2].bias))
+                d["qkv2"] = pack_linear(torch.cat([a2.to_q.weight, a2.to_k.weight, a2.to_v.weight], 0), dt, on("qkv"))
+            d["o2"] = (pack_linear(a2.to_out[0].weight, dt, on("o")), _f32(a2.to_out[0].bias))
+            d["ff1"] = pack_geglu(tb.ff.net[0].proj.weight, tb.ff.net[0].proj.bias, dt, on("ff1"))
+            d["ff2"] = (pack_linear(tb.ff.net[2].weight, dt, on("ff2")), _f32(tb.ff.net[2].bias))
             return d
 
         def pack_tx(m, cross, name):
             d = {"gn": (_f32(m.norm.weight), _f32(m.norm.bias))}
-            with split_weights(self._kind_on(name, "pin")):
-                d["pin"] = (pack_linear(m.proj_in.weight, dt), _f32(m.proj_in.bias))
-            wpo = pack_linear(m.proj_out.weight)
+            d["pin"] = (pack_linear(m.proj_in.weight, dt, self._two_term(name, "pin")), _f32(m.proj_in.bias))
+            wpo = rows_linear(m.proj_out.weight)
             if self._asplit:                      # two-term token stream [t_hi | t_lo]: the weight appears twice
                 wpo = torch.cat([wpo, wpo], 1)
-            with split_weights(self._kind_on(name, "pout")):
-                d["pout"] = (_w16(wpo, dt), _f32(m.proj_out.bias))
+            d["pout"] = (_w16(wpo, dt, self._two_term(name, "pout")), _f32(m.proj_out.bias))
             d["tb"] = pack_tblock(m.transformer_blocks[0], cross, name)
             return d
 
         for name, m in self.named_modules():
-            with split_weights(self._wants_split(name)):
-                if isinstance(m, _ResBlockP):
-                    P[name] = pack_res(m, name)
-                elif isinstance(m, _SpatialTransformerP):
-                    P[name] = pack_tx(m, True, name)
-                elif isinstance(m, _TemporalTransformerP):
-                    P[name] = pack_tx(m, False, name)
-                elif isinstance(m, _DownP):
-                    with split_weights(self._kind_on(name, "resample")):
-                        P[name] = (pack_conv3x3(m.op.weight, dt), _f32(m.op.bias))
-                elif isinstance(m, _UpP):
-                    with split_weights(self._kind_on(name, "resample")):
-                        P[name] = (pack_conv3x3(m.conv.weight, dt), _f32(m.conv.bias))
+            if isinstance(m, _ResBlockP):
+                P[name] = pack_res(m, name)
+            elif isinstance(m, _SpatialTransformerP):
+                P[name] = pack_tx(m, True, name)
+            elif isinstance(m, _TemporalTransformerP):
+                P[name] = pack_tx(m, False, name)
+            elif isinstance(m, _DownP):
+                P[name] = (pack_conv3x3(m.op.weight, dt, self._two_term(name, "resample")), _f32(m.op.bias))
+            elif isinstance(m, _UpP):
+                P[name] = (pack_conv3x3(m.conv.weight, dt, self._two_term(name, "resample")), _f32(m.conv.bias))
             m._pname = name
         P["head_gn"] = (_f32(self.out[0].weight), _f32(self.out[0].bias))
-        with split_weights(self._wants_split("out")):
-            P["head_conv"] = (pack_conv3x3(self.out[2].weight, dt), _f32(self.out[2].bias))
+        P["head_conv"] = (pack_conv3x3(self.out[2].weight, dt, self._two_term("out", "head")), _f32(self.out[2].bias))
         eye = torch.eye(self.out_dim, dtype=torch.float32, device=self.out[2].weight.device)
         P["eye"] = eye.contiguous()
         self._packed = P
@@ -690,20 +650,19 @@ class UNetSD_T2VBase(nn.Module):
         (vgen_amd/unet_dreamvideo.py).  T: the block's packed dict; geom: (units, F, H*W) of a temporal block's rows."""
         return tok
 
-    def _tblock(self, P, x, M, d, heads, attn1, attn2, geom=None):
-        """reference: BasicTransformerBlock.forward (util.py:700-704); x is the fp32 token stream."""
-        be = ops.backend()
+    # reference: BasicTransformerBlock.forward (util.py:700-704) on the fp32 token stream, in two pieces.  T: the block's packed
+    # dict; geom: see _adapt
+    def _attn_branch(self, T, i, tok, M, attn, geom=None):
+        """tok + to_out(attn(norm_i(tok))), i = 1 | 2; `attn`: the 16-bit normed tokens -> the attention output [M, d]."""
+        n = ops.backend().layernorm(tok, *T[f"ln{i}"], 1e-5, self.compute_dtype)
+        return self._linear(attn(n), T[f"o{i}"], M, residual=self._adapt(T, f"a{i}", tok, M, geom))
+
+    def _ff(self, T, tok, M, geom=None):
+        """tok + ff(norm3(tok)); the sum is only consumed by proj_out -> emitted as its 16-bit operand (_ff_out)."""
         dt = self.compute_dtype
-        n = be.layernorm(x, *P["ln1"], 1e-5, dt)
-        qkv = self._linear(n, P["qkv1"], M, out_dtype=dt)
-        o = attn1(qkv)
-        x = self._linear(o, P["o1"], M, residual=self._adapt(P, "a1", x, M, geom))
-        n = be.layernorm(x, *P["ln2"], 1e-5, dt)
-        o = attn2(n)
-        x = self._linear(o, P["o2"], M, residual=self._adapt(P, "a2", x, M, geom))
-        n = be.layernorm(x, *P["ln3"], 1e-5, dt)
-        g = self._linear(n, P["ff1"], M, out_dtype=dt, epilogue=L.EPI_GEGLU)
-        return self._ff_out(g, P["ff2"], M, self._adapt(P, "ff", x, M, geom))
+        n = ops.backend().layernorm(tok, *T["ln3"], 1e-5, dt)
+        g = self._linear(n, T["ff1"], M, out_dtype=dt, epilogue=L.EPI_GEGLU)
+        return self._ff_out(g, T["ff2"], M, self._adapt(T, "ff", tok, M, geom))
 
     def _ff_out(self, g, ff2, M, tok):
         """tok + FF-out, as the A operand of proj_out: emitted 16-bit straight from the GEMM's epilogue (sum formed in fp32)
@@ -730,14 +689,16 @@ class UNetSD_T2VBase(nn.Module):
         scale = HEAD_DIM ** -0.5
         a, _ = be.groupnorm(x, None, Bp * F, N, 32, 1e-6, *P["gn"], False, False, dt)
         tok = self._linear(a, P["pin"], Mp)
-        # x = x + attn1(norm1(x))
-        n = be.layernorm(tok, *T["ln1"], 1e-5, dt)
-        qkv = self._linear(n, T["qkv1"], Mp, out_dtype=dt)
-        o = torch.empty((Mp, d), dtype=dt, device=qkv.device)
-        ld = 3 * d
-        be.attention(Attn(q=qkv, k=qkv[:, d:], v=qkv[:, 2 * d:], out=o, heads=heads, nq=N, nk=N, nbatch=Bp * F, inner=1,
-                          q_s=(ld, N * ld, 0), k_s=(ld, N * ld, 0), v_s=(ld, N * ld, 0), o_s=(d, N * d, 0), scale=scale))
-        tok = self._linear(o, T["o1"], Mp, residual=self._adapt(T, "a1", tok, Mp))
+
+        def self_attn(n):
+            qkv = self._linear(n, T["qkv1"], Mp, out_dtype=dt)
+            o = torch.empty((Mp, d), dtype=dt, device=qkv.device)
+            ld = 3 * d
+            be.attention(Attn(q=qkv, k=qkv[:, d:], v=qkv[:, 2 * d:], out=o, heads=heads, nq=N, nk=N, nbatch=Bp * F, inner=1,
+                              q_s=(ld, N * ld, 0), k_s=(ld, N * ld, 0), v_s=(ld, N * ld, 0), o_s=(d, N * d, 0), scale=scale))
+            return o
+
+        tok = self._attn_branch(T, 1, tok, Mp, self_attn)
         # x = x + attn2(norm2(x), context): the query side first — the last context-free step
         n = be.layernorm(tok, *T["ln2"], 1e-5, dt)
         q = self._linear(n, T["q2"], Mp, out_dtype=dt)
@@ -753,11 +714,7 @@ class UNetSD_T2VBase(nn.Module):
         be.attention(Attn(q=q, k=k, v=v, out=o, heads=heads, nq=N, nk=Lctx, nbatch=B * F, inner=F,
                           q_s=(d, F * N * d, N * d), k_s=kvs, v_s=kvs, o_s=(d, F * N * d, N * d), scale=scale))
         tok = self._linear(o, T["o2"], M, residual=self._adapt(T, "a2", tok, M))
-        # x = x + ff(norm3(x)); the FF output is only consumed by proj_out -> emitted 16-bit (sum formed in fp32)
-        n = be.layernorm(tok, *T["ln3"], 1e-5, dt)
-        g = self._linear(n, T["ff1"], M, out_dtype=dt, epilogue=L.EPI_GEGLU)
-        t = self._ff_out(g, T["ff2"], M, self._adapt(T, "ff", tok, M))
-        return self._linear(t, P["pout"], M, residual=x, colstats=True, alg_k=d)
+        return self._linear(self._ff(T, tok, M), P["pout"], M, residual=x, colstats=True, alg_k=d)
 
     def _temporal_tx(self, tt: _TemporalTransformerP, x, B, F, H, W):
         """reference: TemporalTransformer.forward (util.py:1240-1286), only_self_att=True."""
@@ -770,20 +727,22 @@ class UNetSD_T2VBase(nn.Module):
         a, _ = be.groupnorm(x, None, B, F * S, 32, 1e-6, *P["gn"], False, False, dt)
         tok = self._linear(a, P["pin"], M)
         scale = HEAD_DIM ** -0.5
+        T, geom = P["tb"], (B, F, S)
 
-        def self_attn(qkv):
-            out = torch.empty((M, d), dtype=dt, device=qkv.device)
-            ld = 3 * d
-            s3 = (S * ld, F * S * ld, ld)   # rows = frames, sequences = (b, pixel)
-            return be.attention(Attn(q=qkv, k=qkv[:, d:], v=qkv[:, 2 * d:], out=out, heads=heads,
-                                     nq=F, nk=F, nbatch=B * S, inner=S, q_s=s3, k_s=s3, v_s=s3,
-                                     o_s=(S * d, F * S * d, d), scale=scale))
+        def self_attn(key):
+            def attn(n):
+                qkv = self._linear(n, T[key], M, out_dtype=dt)
+                out = torch.empty((M, d), dtype=dt, device=qkv.device)
+                ld = 3 * d
+                s3 = (S * ld, F * S * ld, ld)   # rows = frames, sequences = (b, pixel)
+                return be.attention(Attn(q=qkv, k=qkv[:, d:], v=qkv[:, 2 * d:], out=out, heads=heads,
+                                         nq=F, nk=F, nbatch=B * S, inner=S, q_s=s3, k_s=s3, v_s=s3,
+                                         o_s=(S * d, F * S * d, d), scale=scale))
+            return attn
 
-        def attn2(n):
-            return self_attn(self._linear(n, P["tb"]["qkv2"], M, out_dtype=dt))
-
-        t = self._tblock(P["tb"], tok, M, d, heads, self_attn, attn2, geom=(B, F, S))
-        return self._linear(t, P["pout"], M, residual=x, colstats=True, alg_k=d)
+        tok = self._attn_branch(T, 1, tok, M, self_attn("qkv1"), geom)
+        tok = self._attn_branch(T, 2, tok, M, self_attn("qkv2"), geom)
+        return self._linear(self._ff(T, tok, M, geom), P["pout"], M, residual=x, colstats=True, alg_k=d)
 
     # -- forward -------------------------------------------------------------------------------
     def _prepare_units(self, shape, device, kwargs_list):

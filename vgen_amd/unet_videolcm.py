@@ -136,7 +136,9 @@ class _ComposerTrunk(UNetSD_T2VBase):
         be, dt = ops.backend(), self.compute_dtype
         if self._pic is None:
             l0, l2 = self.pre_image_condition[0], self.pre_image_condition[2]
-            self._pic = ((pack_linear(l0.weight, dt), _f32(l0.bias)), (pack_linear(l2.weight, dt), _f32(l2.bias)))
+            # single-pass in every mode: `_pic` lives outside `_packed`, the precision rule and the calibration file
+            self._pic = ((pack_linear(l0.weight, dt, split=False), _f32(l0.bias)),
+                         (pack_linear(l2.weight, dt, split=False), _f32(l2.bias)))
         x = image.to(dtype=torch.float32).reshape(B, self.context_dim).contiguous()
         h = self._linear(be.act_cast(x, 0, dt), self._pic[0], B)
         o = self._linear(be.act_cast(h, 1, dt), self._pic[1], B)

@@ -23,7 +23,7 @@ import torch.nn as nn
 from . import lib as L
 from . import ops
 from .ops import TapGemm
-from .unet import _f32, _w16_cat, pack_conv3x3, pack_linear, pack_small_conv3x3, split_weights
+from .unet import _f32, _w16_cat, pack_conv3x3, pack_linear, pack_small_conv3x3, rows_conv3x3, rows_linear
 
 
 def _norm(c):
@@ -284,8 +284,7 @@ class AutoencoderKL(nn.Module):
     # -- packing ---------------------------------------------------------------------------------
     @torch.no_grad()
     def pack(self):
-        with split_weights(self.precision == "high"):
-            P = self._pack()
+        P = self._pack()
         if self.precision == "calibrated":
             from .calibrate import load_calibrated
             load_calibrated(self, self.calibration)
@@ -293,37 +292,38 @@ class AutoencoderKL(nn.Module):
 
     def _pack(self):
         dt = self.compute_dtype
+        split = self.precision == "high"            # every packed weight two-term, or none
         P = {}
         for name, m in self.named_modules():
             m._pname = name
             if isinstance(m, _ResnetBlockP):
                 d = {"gn1": (_f32(m.norm1.weight), _f32(m.norm1.bias)),
-                     "conv1": (pack_conv3x3(m.conv1.weight, dt), _f32(m.conv1.bias)),
+                     "conv1": (pack_conv3x3(m.conv1.weight, dt, split), _f32(m.conv1.bias)),
                      "gn2": (_f32(m.norm2.weight), _f32(m.norm2.bias))}
                 b2 = _f32(m.conv2.bias)
                 if m.cin != m.cout:
-                    w2 = _w16_cat([pack_conv3x3(m.conv2.weight), pack_linear(m.nin_shortcut.weight)], dt)
+                    w2 = _w16_cat([rows_conv3x3(m.conv2.weight), rows_linear(m.nin_shortcut.weight)], dt, split)
                     b2 = (b2 + _f32(m.nin_shortcut.bias)).contiguous()
                 else:
-                    w2 = pack_conv3x3(m.conv2.weight, dt)
+                    w2 = pack_conv3x3(m.conv2.weight, dt, split)
                 d["conv2"] = (w2, b2)
                 P[name] = d
             elif isinstance(m, _AttnBlockP):
                 P[name] = {
                     "gn": (_f32(m.norm.weight), _f32(m.norm.bias)),
-                    "qk": (pack_linear(torch.cat([m.q.weight, m.k.weight], 0), dt),
+                    "qk": (pack_linear(torch.cat([m.q.weight, m.k.weight], 0), dt, split),
                            torch.cat([_f32(m.q.bias), _f32(m.k.bias)]).contiguous()),
-                    "v": pack_linear(m.v.weight, dt), "vb": _f32(m.v.bias),
-                    "o": (pack_linear(m.proj_out.weight, dt), _f32(m.proj_out.bias))}
+                    "v": pack_linear(m.v.weight, dt, split), "vb": _f32(m.v.bias),
+                    "o": (pack_linear(m.proj_out.weight, dt, split), _f32(m.proj_out.bias))}
             elif isinstance(m, _ResampleP):
-                P[name] = (pack_conv3x3(m.conv.weight, dt), _f32(m.conv.bias))
+                P[name] = (pack_conv3x3(m.conv.weight, dt, split), _f32(m.conv.bias))
         for side in ("encoder", "decoder"):
             net = getattr(self, side)
             ci = net.conv_in
             kpad = ((27 * ci.in_channels + 63) // 64) * 64          # split stem: fp32-accurate input / weights
             P[side + ".conv_in"] = (pack_small_conv3x3(ci.weight, kpad, dt, split=True), _f32(ci.bias), kpad)
             P[side + ".norm_out"] = (_f32(net.norm_out.weight), _f32(net.norm_out.bias))
-            P[side + ".conv_out"] = (pack_conv3x3(net.conv_out.weight, dt), _f32(net.conv_out.bias))
+            P[side + ".conv_out"] = (pack_conv3x3(net.conv_out.weight, dt, split), _f32(net.conv_out.bias))
         for nm in ("quant_conv", "post_quant_conv"):
             c = getattr(self, nm)
             P[nm] = (_f32(c.weight.reshape(c.out_channels, c.in_channels)), _f32(c.bias))
