@@ -436,6 +436,87 @@ int vgen_adapter(const float* x, int64_t ldx, int64_t M, int32_t d, int32_t h, i
                  const void* Wu, const float* bu, const float* hb, int64_t ldhb, int64_t rows_per_hb, float* out,
                  int64_t ldo, int32_t dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Sketch annotator, part 1 (the second net of the two): the sketch-simplification net ("cleaner", tools/annotator/sketch/sketch_simplification.py:27-73;
+ * the engines call it as `sketch = 1.0 - cleaner(1.0 - sketch)`, tools/inferences/inference_tft2v_vcomposer_entrance.py:417).
+ *
+ * Arithmetic contract.  Activations are rows x channels as everywhere else, 16-bit, with the channel count zero-padded to a
+ * multiple of 64 (48 and 24 -> 64); padded channels of weights and biases are zero, so padded activations stay exactly
+ * zero.  Every dense 3x3 conv (stride 1 | 2, pad 1) is ONE vgen_tapgemm launch (VGEN_TAP_CONV3X3) with a 16-bit output,
+ * followed by vgen_relu_shuffle16 (g = 1, in place).  ConvTranspose2d(C, C, 4, 2, 1) (:56,62,68) is ONE 3x3 / stride-1 /
+ * pad-1 tap-GEMM launch with N = 4 C output columns ordered (py, px, co):
+ *     W'[(py, px, co), (dy + 1, dx + 1), ci] = Wt[ci, co, py + 1 - 2 dy, px + 1 - 2 dx]   where that index is in 0..3, else 0
+ * (output pixel (2 y + py, 2 x + px) gathers input pixel (y + dy, x + dx) through kernel tap ky = py + 1 - 2 dy), bias
+ * b[co] at all four (py, px); vgen_relu_shuffle16 (g = 2) then does the depth-to-space and the ReLU.  16 of the 36
+ * (parity, tap) pairs are non-zero: 2.25x the layer's FLOPs, +7 % on the net.  The one-channel stem and the 24 -> 1 head
+ * are fp32 kernels (fp32 weights, fp32 accumulation in one fixed order: bias, then taps row-major, channels ascending, one
+ * fused multiply-add each).
+ *
+ * vgen_sketch_stem: [1 - x], (. - mean) / std (:78), Conv2d(1, 48, 5, 2, 2) + bias + ReLU (:28-29).
+ *   x     fp32 [n, 1, H, W] contiguous, H and W even;  flip != 0: the conv sees 1 - x (the engine's inner `1.0 - sketch`).
+ *         The conv pads the NORMALISED image with zeros; out-of-image taps are never read.
+ *   w     fp32 [25, 64]: w[ky * 5 + kx, co] = weight[co, 0, ky, kx], columns 48..63 zero;  b fp32 [64], likewise.
+ *   out   `dtype` rows [n * H/2 * W/2, 64], row stride ldo (>= 64, % 8 == 0): relu(.) rounded to nearest even.
+ * vgen_relu_shuffle16: 16-bit rows `in` [M, g^2 C] (row stride ldi) -> out[(img, g y + py, g x + px), c] =
+ *   relu(in[(img, y, x), (py * g + px) * C + c]), rows [M g^2, C] (row stride ldo); g in {1, 2}; M = images x Hin x Win
+ *   (g = 1 ignores Hin / Win).  Negative values (and -0) become +0, NaN and everything else keep their bits: bit-exact
+ *   against relu(pixel_shuffle) by construction.  C % 8 == 0.  out may alias in ONLY as the exact in-place form of g = 1
+ *   (out == in, ldo == ldi); any other overlap is rejected.
+ * vgen_sketch_head: Conv2d(24, 1, 3, 1, 1) + bias + sigmoid (:72-73) [, 1 - . : the engine's outer `1.0 -`].
+ *   a     `dtype` rows [n * H * W, >= C] (row stride lda), C % 8 == 0, C <= 64;  w fp32 [9, C]: w[ky * 3 + kx, c];
+ *   out   fp32 [n, 1, H, W] = sigmoid(v) or 1 - sigmoid(v), sigmoid(v) = 1 / (1 + expf(-v)).
+ * All three only enqueue, touch no row or column outside their operands and return VGEN_E_BADARG (with a message) for an
+ * argument error before anything is launched. */
+int vgen_sketch_stem(const float* x, int64_t n, int32_t H, int32_t W, int32_t flip, float mean, float stdv,
+                     const float* w, const float* b, void* out, int64_t ldo, int32_t dtype, void* stream);
+int vgen_relu_shuffle16(const void* in, int64_t ldi, int64_t M, int32_t C, int32_t g, int32_t Hin, int32_t Win,
+                        void* out, int64_t ldo, int32_t dtype, void* stream);
+int vgen_sketch_head(const void* a, int64_t lda, int64_t n, int32_t H, int32_t W, int32_t C, const float* w,
+                     float bias, int32_t flip, float* out, int32_t dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Sketch annotator, part 2: PiDiNet (tools/annotator/sketch/pidinet.py:527-704, the converted "vanilla CNN" form that
+ * pidinet_bsd(vanilla_cnn=True) builds, :732-746; called at tools/inferences/inference_tft2v_vcomposer_entrance.py:416).
+ *
+ * Arithmetic contract.  The stream is fp32 rows x channels, channel counts zero-padded to a multiple of 64 (60 / 120 / 240
+ * -> 64 / 128 / 256; padded weights and biases are zero, so padded activations stay exactly zero).
+ *   stem     the 3 -> 60 init_block (:576) = vgen_im2col3x3_small(split = 1) + tap-GEMM, like the VAE conv_in.
+ *   block    (PDCBlock_converted, :527-555)  y = vgen_dwconv_relu(x): depthwise conv in fp32 (weights, accumulation, fixed
+ *            tap order), ReLU, rounded ONCE to 16 bit = the A operand of the 1x1 conv2, a tap-GEMM launch with the block
+ *            input as fp32 `residual`.  Stride-2 blocks: 2x2 max-pool first (pool = 1), then conv2 with the 16-bit pooled
+ *            input as the second K segment (A2, C2) carrying the 1x1 shortcut; the shortcut's bias is the launch's bias.
+ *   side head per scale i (CDCM :466-488, CSAM :444-464, MapReduce :490-500), regrouped so that 5 floats per pixel leave
+ *            the heavy kernel:  t = conv1(relu(x_i)) + b  (ReLU-cast: vgen_dwconv_relu k = 1; 1x1 conv: tap-GEMM, 16-bit out,
+ *            24 channels padded to 32);  u = sum of the four dilated 3x3 convs of t (dilations 5, 7, 9, 11, zero padding);
+ *            m = Wa . relu(u) + ba (CSAM.conv1, 4 channels),  r = wr . u (MapReduce without its bias)   [vgen_cdcm_head]
+ *            e_i = sigmoid(conv3x3(m)) * r + br  — because x_fuse = u * y with y one channel, conv_reduce(u * y) = y (wr . u)
+ *            + br; the 3x3 conv pads m (bias ba included) with zeros                                      [vgen_pidinet_emap]
+ *   output   sigmoid(bc + sum_i wc_i * bilinear_{align_corners=False}(e_i -> H x W))  (:687-704)           [vgen_pidinet_fuse]
+ *
+ * vgen_dwconv_relu: x fp32 rows [n H W, Cp] (row stride ldx), Cp % 64 == 0; w fp32 [k * k, Cp] (w[ky * k + kx, c] =
+ *   conv1.weight[c, 0, ky, kx]), k in {3, 5}, pad k / 2, out-of-image taps are zeros (never reads);
+ *   y[m, c] = round16(relu(sum_taps w x)), contiguous rows [M, Cp], accumulated from 0 with one fused multiply-add per tap
+ *   in (ky, kx) order.  k = 1 with w = NULL: y = round16(relu(x)).  pool = 1: H and W even; xp (fp32) and xp16 (its 16-bit
+ *   cast), contiguous [n H/2 W/2, Cp], receive the 2x2 / stride-2 max-pool of x, and the conv runs on xp (two launches).
+ *   pool = 0: xp = xp16 = NULL.
+ * vgen_cdcm_head: t `dtype` rows [n H W, >= 32] (row stride ldt; channels 24..31 zero); Wd `dtype` [4][9][32][32] =
+ *   conv2_{j+1}.weight[co, ci, ky, kx] at [j][ky * 3 + kx][co][ci], zero-padded; Wa fp32 [4][32], ba fp32 [4], wr fp32 [32].
+ *   The products run on the matrix units (mfma_f32_16x16x32_{f16,bf16}) from an LDS-resident haloed tile (halo 11), u stays
+ *   in fp32 registers; out[m, 0..3] = m, out[m, 4] = r, fp32 rows with stride ldo (>= 5, % 4 == 0); columns >= 5 untouched.
+ * vgen_pidinet_emap: mr = those rows (stride ld); w2 fp32 [9][4] = CSAM.conv2.weight[0, j, ky, kx] at [ky * 3 + kx][j];
+ *   e fp32 [n, H, W].
+ * vgen_pidinet_fuse: e0..e3 fp32 maps [n, H >> i, W >> i] (H, W multiples of 8: every ratio is a power of two, the
+ *   interpolation weights are exact); out fp32 [n, 1, H, W].
+ * All four only enqueue, validate first (VGEN_E_BADARG + message) and touch nothing outside their operands. */
+int vgen_dwconv_relu(const float* x, int64_t ldx, int64_t n, int32_t H, int32_t W, int32_t Cp, const float* w,
+                     int32_t k, int32_t pool, float* xp, void* xp16, void* y, int32_t dtype, void* stream);
+int vgen_cdcm_head(const void* t, int64_t ldt, int64_t n, int32_t H, int32_t W, const void* Wd, const float* Wa,
+                   const float* ba, const float* wr, float* out, int64_t ldo, int32_t dtype, void* stream);
+int vgen_pidinet_emap(const float* mr, int64_t ld, int64_t n, int32_t H, int32_t W, const float* w2, float br,
+                      float* e, void* stream);
+int vgen_pidinet_fuse(const float* e0, const float* e1, const float* e2, const float* e3, int64_t n, int32_t H,
+                      int32_t W, float wc0, float wc1, float wc2, float wc3, float bc, float* out, void* stream);
+
 /* Glue of a sampling session's step graph (vgen_amd/session.py), so that a captured step holds only this library's
  * launches.  vgen_repeat_rows: dst[g*bytes .. (g+1)*bytes) = src[0 .. bytes) for g < G — the rows of the context-free
  * prefix shared by a classifier-free-guidance pair (diffusion_ddim.py:157-158 evaluates it per branch) fanned out to

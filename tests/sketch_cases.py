@@ -1,0 +1,192 @@
+"""Kernels of csrc/sketch.hip: seeded operands, fp64 references and DERIVED per-element bounds (tests/test_sketch.py).
+
+u32 = 2^-24 is the unit roundoff of fp32.  A sum of K products accumulated in fp32 in ANY order (fmaf chain, MFMA) deviates
+from the exact sum of the same operands by at most (K + 2) u32 sum |w| |a| (first order; the + 2 covers a bias and one final
+operation).  A value that is then rounded to a 16-bit format is checked as an INTERVAL: rounding is monotone, so the device
+value must lie in [r16(v - e), r16(v + e)] — zero width unless the fp32 uncertainty straddles a rounding boundary.  sigmoid
+evaluated as 1 / (1 + expf(-v)): Lipschitz 1/4 in v, plus expf to 3 ulp (6 u32 relative, times s (1 - s) <= 1/4), the add,
+the division and an optional 1 - s at u32 each of values <= 1: 8 u32 absolute in all.  Nothing is fitted to device output.
+
+The model-level tolerance is the issue's: 1.25 x the fixture's stored autocast yardstick (rel-L2, per output, per dtype)."""
+import torch
+import torch.nn.functional as F
+
+U32 = 2.0 ** -24
+SIG_ABS = 8 * U32
+TOL = 1.25
+
+
+def dt_of(name):
+    return torch.float16 if name == "fp16" else torch.bfloat16
+
+
+def r16(v, dt):
+    return v.float().to(dt).double()
+
+
+def _gen(*key):
+    s = 0
+    for k in key:
+        s = s * 1009 + int(k)
+    return torch.Generator("cpu").manual_seed(s % (2 ** 31))
+
+
+def inside(out, lo, hi):
+    """Fraction-free interval check; returns the number of elements outside [lo, hi]."""
+    o = out.double().cpu()
+    return int(((o < lo) | (o > hi)).sum())
+
+
+def worst(out, ref, bound):
+    return float(((out.double().cpu() - ref).abs() / bound.clamp_min(1e-300)).max())
+
+
+# ---- vgen_dwconv_relu ------------------------------------------------------------------------------------------------------
+def dw_operands(n, H, W, Cp, k, seed=0):
+    g = _gen(1, n, H, W, Cp, k, seed)
+    x = torch.randn(n * H * W, Cp, generator=g) * 1.5 + torch.randn(1, Cp, generator=g)
+    w = torch.randn(k * k, Cp, generator=g) / k if k > 1 else None
+    return x, w
+
+
+def dw_reference(x, w, n, H, W, k, dt, pool):
+    """(lo, hi) interval of the 16-bit conv rows [M, Cp] (+ exact pooled rows when pool)."""
+    Cp = x.shape[1]
+    img = x.double().view(n, H, W, Cp).permute(0, 3, 1, 2)
+    xp = None
+    if pool:
+        img = F.max_pool2d(img, 2, 2)
+        xp = img.permute(0, 2, 3, 1).reshape(-1, Cp)
+    if k == 1:
+        v, e = img, torch.zeros_like(img)
+    else:
+        wk = w.double().t().reshape(Cp, 1, k, k)
+        v = F.conv2d(img, wk, padding=k // 2, groups=Cp)
+        e = (k * k + 2) * U32 * F.conv2d(img.abs(), wk.abs(), padding=k // 2, groups=Cp)
+    rows = lambda t: t.permute(0, 2, 3, 1).reshape(-1, Cp)
+    lo, hi = r16(torch.relu(rows(v - e)), dt), r16(torch.relu(rows(v + e)), dt)
+    return lo, hi, xp
+
+
+# ---- vgen_cdcm_head ----------------------------------------------------------------------------------------------------------
+def cdcm_operands(n, H, W, dt, seed=0, d=24):
+    g = _gen(2, n, H, W, seed)
+    t = torch.zeros(n * H * W, 32)
+    t[:, :d] = torch.randn(n * H * W, d, generator=g)
+    Wd = torch.zeros(4, 9, 32, 32)
+    Wd[:, :, :d, :d] = torch.randn(4, 9, d, d, generator=g) / (36 * d) ** 0.5
+    Wa = torch.zeros(4, 32)
+    Wa[:, :d] = torch.randn(4, d, generator=g) / d ** 0.5
+    wr = torch.zeros(32)
+    wr[:d] = torch.randn(d, generator=g) / d ** 0.5
+    ba = 0.1 * torch.randn(4, generator=g)
+    return dict(t=t.to(dt), Wd=Wd.to(dt), Wa=Wa, ba=ba, wr=wr, n=n, H=H, W=W)
+
+
+def cdcm_reference(op):
+    """(ref [M, 5], bound [M, 5]) in fp64 from the SAME 16-bit operands."""
+    n, H, W = op["n"], op["H"], op["W"]
+    t = op["t"].double().view(n, H, W, 32).permute(0, 3, 1, 2)
+    u = torch.zeros(n, 32, H, W, dtype=torch.float64)
+    ua = torch.zeros_like(u)
+    for j, dil in enumerate((5, 7, 9, 11)):
+        wk = op["Wd"][j].double().view(3, 3, 32, 32).permute(2, 3, 0, 1)
+        u += F.conv2d(t, wk, padding=dil, dilation=dil)
+        ua += F.conv2d(t.abs(), wk.abs(), padding=dil, dilation=dil)
+    rows = lambda v: v.permute(0, 2, 3, 1).reshape(-1, 32)
+    u, e_u = rows(u), (36 * 32 + 2) * U32 * rows(ua)
+    Wa, wr, ba = op["Wa"].double(), op["wr"].double(), op["ba"].double()
+    m = torch.relu(u) @ Wa.t() + ba
+    e_m = e_u @ Wa.abs().t() + (32 + 3) * U32 * ((torch.relu(u) + e_u) @ Wa.abs().t() + ba.abs())
+    r = u @ wr
+    e_r = e_u @ wr.abs() + (32 + 3) * U32 * ((u.abs() + e_u) @ wr.abs())
+    return torch.cat([m, r[:, None]], 1), torch.cat([e_m, e_r[:, None]], 1)
+
+
+# ---- vgen_pidinet_emap / vgen_pidinet_fuse ------------------------------------------------------------------------------------
+def emap_operands(n, H, W, seed=0):
+    g = _gen(3, n, H, W, seed)
+    mr = torch.randn(n * H * W, 8, generator=g)
+    w2 = torch.randn(9, 4, generator=g) / 3
+    return mr, w2, 0.37
+
+
+def emap_reference(mr, w2, br, n, H, W):
+    m = mr[:, :4].double().view(n, H, W, 4).permute(0, 3, 1, 2)
+    wk = w2.double().view(3, 3, 4).permute(2, 0, 1)[None]
+    s = F.conv2d(m, wk, padding=1)[:, 0]
+    e_s = (36 + 2) * U32 * F.conv2d(m.abs(), wk.abs(), padding=1)[:, 0]
+    sig = torch.sigmoid(s)
+    r = mr[:, 4].double().view(n, H, W)
+    ref = sig * r + br
+    bound = r.abs() * (0.25 * e_s + SIG_ABS) + 2 * U32 * ((sig * r).abs() + abs(br))
+    return ref, bound
+
+
+def fuse_operands(n, H, W, seed=0):
+    g = _gen(4, n, H, W, seed)
+    es = [torch.randn(n, H >> i, W >> i, generator=g) * 1.5 for i in range(4)]
+    return es, [0.4, -0.3, 0.25, 0.6], -0.1
+
+
+def fuse_reference(es, wc, bc, H, W):
+    acc = torch.full((es[0].shape[0], H, W), float(bc), dtype=torch.float64)
+    mag = torch.full_like(acc, abs(bc))
+    e_b = torch.zeros_like(acc)
+    for e, w in zip(es, wc):
+        up = F.interpolate(e.double()[:, None], (H, W), mode="bilinear", align_corners=False)[:, 0]
+        upa = F.interpolate(e.double().abs()[:, None], (H, W), mode="bilinear", align_corners=False)[:, 0]
+        acc += w * up
+        mag += abs(w) * upa
+        e_b += abs(w) * 4 * U32 * upa            # three fp32 products / sums deep, on exact power-of-two-ratio weights
+    e_acc = e_b + (4 + 2) * U32 * mag
+    return torch.sigmoid(acc)[:, None], (0.25 * e_acc + SIG_ABS)[:, None]
+
+
+# ---- vgen_sketch_stem / vgen_sketch_head / vgen_relu_shuffle16 ----------------------------------------------------------------
+def stem_operands(n, H, W, seed=0):
+    g = _gen(5, n, H, W, seed)
+    x = torch.rand(n, 1, H, W, generator=g)
+    w = torch.zeros(25, 64)
+    w[:, :48] = torch.randn(25, 48, generator=g) / 5
+    b = torch.zeros(64)
+    b[:48] = 0.1 * torch.randn(48, generator=g)
+    return x, w, b, 0.9664114577640158, 0.0858381272736797
+
+
+def stem_reference(x, w, b, mean, std, flip, dt):
+    mean, std = float(torch.tensor(mean, dtype=torch.float32)), float(torch.tensor(std, dtype=torch.float32))
+    xd = x.double()
+    xf = 1.0 - xd if flip else xd
+    v = (xf - mean) / std
+    e_v = U32 * 3 * (xf.abs() + abs(mean)) / std          # the fp32 1 - x, the subtraction and the division
+    wk = w.double().t().reshape(64, 1, 5, 5)
+    acc = F.conv2d(v, wk, b.double(), stride=2, padding=2)
+    e = F.conv2d(e_v, wk.abs(), stride=2, padding=2) + \
+        (25 + 2) * U32 * (F.conv2d(v.abs(), wk.abs(), stride=2, padding=2) + b.double().abs().view(1, -1, 1, 1))
+    rows = lambda t: t.permute(0, 2, 3, 1).reshape(-1, 64)
+    return r16(torch.relu(rows(acc - e)), dt), r16(torch.relu(rows(acc + e)), dt)
+
+
+def head_operands(n, H, W, dt, C=24, seed=0):
+    g = _gen(6, n, H, W, C, seed)
+    a = torch.zeros(n * H * W, 64)
+    a[:, :C] = torch.relu(torch.randn(n * H * W, C, generator=g))
+    w = torch.randn(9, C, generator=g) / (9 * C) ** 0.5 * 3
+    return a.to(dt), w, 0.2
+
+
+def head_reference(a, w, bias, n, H, W, flip):
+    C = w.shape[1]
+    img = a[:, :C].double().view(n, H, W, C).permute(0, 3, 1, 2)
+    wk = w.double().view(3, 3, C).permute(2, 0, 1)[None]
+    v = F.conv2d(img, wk, padding=1) + bias
+    e = (9 * C + 2) * U32 * (F.conv2d(img.abs(), wk.abs(), padding=1) + abs(bias))
+    s = torch.sigmoid(v)
+    return (1.0 - s if flip else s), 0.25 * e + SIG_ABS
+
+
+def shuffle_reference(a, C, g, n, Hin, Win):
+    """relu(pixel_shuffle) of rows [n Hin Win, g*g*C] with columns (py, px, c) -> rows [n gHin gWin, C]."""
+    v = torch.relu(a[:, : g * g * C].float()).view(n, Hin, Win, g, g, C)
+    return v.permute(0, 1, 3, 2, 4, 5).reshape(n * g * Hin * g * Win, C).to(a.dtype)

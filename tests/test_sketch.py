@@ -1,0 +1,653 @@
+"""vgen_amd/sketch.py — native PiDiNet + sketch simplification (the `sketch` / `single_sketch` conditions of the VideoComposer
+configs) and the kernels of csrc/sketch.hip.
+
+CPU: structure, checkpoint conversion, packing, the ABI contract, the tiny fixture on the ABI emulator.  GPU: every kernel per
+element against fp64 torch ops on the same operands under the derived bounds of tests/sketch_cases.py, canaries around every
+output, the fixtures within 1.25 x the reference's own autocast yardstick.
+
+Measured on one MI355X, err / yardstick: tiny fp16 edge 0.66-0.73, sketch 0.88, clean 0.89-0.90; tiny bf16 0.48-0.49, 0.78-0.82,
+0.84-0.85; full fp16 edge 0.77 (9.36e-4), sketch 0.90 (7.07e-4), clean 0.90 (5.45e-4): nothing above 1.0."""
+import ctypes as C
+import importlib.util
+import os
+import re
+import subprocess
+import sys
+import types
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import sketch_cases as sc
+from conftest import GOLD, ROOT, gold, rel_l2
+from oracle.abi_emulator import EmuBackend
+
+DEV = "cuda:0"
+VGEN_E_BADARG = -1
+
+
+class EmuSketch(EmuBackend):
+    """The ABI emulator plus the seven entry points of csrc/sketch.hip, restated from the header in fp32 torch ops: 16-bit
+    values only where the header rounds, everything else fp32.  Every call is recorded by name."""
+
+    def __init__(self):
+        self.calls = []
+
+    def tapgemm(self, g):
+        self.calls.append("tapgemm")
+        return super().tapgemm(g)
+
+    def im2col3x3_small(self, *a, **k):
+        self.calls.append("im2col3x3_small")
+        return super().im2col3x3_small(*a, **k)
+
+    def sketch_stem(self, x, flip, mean, std, w, b, dt):
+        self.calls.append("sketch_stem")
+        assert x.dtype == torch.float32 and w.shape == (25, 64) and not w[:, 48:].any() and not b[48:].any()
+        v = 1.0 - x if flip else x
+        v = (v - torch.tensor(mean, dtype=torch.float32)) / torch.tensor(std, dtype=torch.float32)
+        y = F.conv2d(v, w.t().reshape(64, 1, 5, 5), b, stride=2, padding=2)
+        return torch.relu(y).permute(0, 2, 3, 1).reshape(-1, 64).to(dt)
+
+    def relu_shuffle16(self, a, C, g=1, Hin=0, Win=0, out=None):
+        self.calls.append("relu_shuffle16")
+        assert a.dtype in (torch.float16, torch.bfloat16) and a.shape[1] >= g * g * C and C % 8 == 0
+        if g == 1:
+            r = torch.relu(a[:, :C].float()).to(a.dtype)
+        else:
+            r = sc.shuffle_reference(a, C, g, a.shape[0] // (Hin * Win), Hin, Win)
+        if out is None and g == 1:
+            out = a
+        if out is None:
+            return r
+        out[:, :C] = r
+        return out
+
+    def sketch_head(self, a, n, H, W, C, w, bias, flip):
+        self.calls.append("sketch_head")
+        img = a[:, :C].float().view(n, H, W, C).permute(0, 3, 1, 2)
+        s = torch.sigmoid(F.conv2d(img, w.view(3, 3, C).permute(2, 0, 1)[None], padding=1) + bias)
+        return 1.0 - s if flip else s
+
+    def dwconv_relu(self, x, n, H, W, w, k, dt, pool=False):
+        self.calls.append("dwconv_relu")
+        Cp = x.shape[1]
+        assert x.dtype == torch.float32 and Cp % 64 == 0 and (w is None) == (k == 1)
+        img = x.view(n, H, W, Cp).permute(0, 3, 1, 2)
+        rows = lambda t: t.permute(0, 2, 3, 1).reshape(-1, Cp).contiguous()
+        if pool:
+            img = F.max_pool2d(img, 2, 2)
+        y = img if k == 1 else F.conv2d(img, w.t().reshape(Cp, 1, k, k), padding=k // 2, groups=Cp)
+        y = rows(torch.relu(y)).to(dt)
+        return (rows(img), rows(img).to(dt), y) if pool else y
+
+    def cdcm_head(self, t, n, H, W, Wd, Wa, ba, wr, out=None):
+        self.calls.append("cdcm_head")
+        assert t.dtype == Wd.dtype and Wd.shape == (4, 9, 32, 32) and t.shape[1] >= 32
+        img = t[:, :32].float().view(n, H, W, 32).permute(0, 3, 1, 2)
+        u = sum(F.conv2d(img, Wd[j].float().view(3, 3, 32, 32).permute(2, 3, 0, 1), padding=d, dilation=d)
+                for j, d in enumerate((5, 7, 9, 11)))
+        u = u.permute(0, 2, 3, 1).reshape(-1, 32)
+        res = torch.zeros(n * H * W, 8) if out is None else out
+        res[:, :4] = torch.relu(u) @ Wa.t() + ba
+        res[:, 4] = u @ wr
+        return res
+
+    def pidinet_emap(self, mr, n, H, W, w2, br):
+        self.calls.append("pidinet_emap")
+        m = mr[:, :4].view(n, H, W, 4).permute(0, 3, 1, 2)
+        s = torch.sigmoid(F.conv2d(m, w2.view(3, 3, 4).permute(2, 0, 1)[None], padding=1))[:, 0]
+        return s * mr[:, 4].view(n, H, W) + br
+
+    def pidinet_fuse(self, es, n, H, W, wc, bc):
+        self.calls.append("pidinet_fuse")
+        acc = torch.full((n, 1, H, W), float(bc))
+        for i, e in enumerate(es):
+            assert tuple(e.shape) == (n, H >> i, W >> i)
+            acc = acc + wc[i] * F.interpolate(e[:, None], (H, W), mode="bilinear", align_corners=False)
+        return torch.sigmoid(acc)
+
+
+@pytest.fixture
+def emu():
+    from vgen_amd import ops
+    be = EmuSketch()
+    prev = ops.set_backend(be)
+    n = torch.get_num_threads()
+    torch.set_num_threads(int(os.environ.get("VGEN_EMU_THREADS", "4")))
+    yield be
+    torch.set_num_threads(n)
+    ops.set_backend(prev)
+
+
+def _gen():
+    spec = importlib.util.spec_from_file_location("make_sketch_golden", os.path.join(GOLD, "make_sketch_golden.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+_MODELS = {}
+
+
+def _models(g, dtname, device="cpu"):
+    """(pidinet, cleaner) with the fixture's seeded weights; built once per (dtype, device) and shared."""
+    key = (dtname, device)
+    if key not in _MODELS:
+        from vgen_amd import sketch
+        from vgen_amd.synth import seeded_state_dict
+        with torch.device("meta"):
+            p = sketch.pidinet_bsd(compute_dtype=dtname)
+            c = sketch.sketch_simplification_gan(compute_dtype=dtname)
+        out = []
+        for m, tag, seed, gain in ((p, "pidinet", g["pidi_seed"], g["pidi_gain"]), (c, "cleaner", g["cleaner_seed"], g["cleaner_gain"])):
+            m = m.to_empty(device="cpu").eval()
+            m.load_state_dict(seeded_state_dict(g["shapes"][tag], seed=seed, gain=gain), strict=True, assign=True)
+            out.append(m.to(device))
+        _MODELS[key] = tuple(out)
+    return _MODELS[key]
+
+
+def _sub(t, step):
+    return t.float().cpu()[:, :, ::step]
+
+
+def _fixture_errs(g, i, dtname, device="cpu"):
+    """rel-L2 of edge, chained sketch and the cleaner alone (from the stored fp16 edge) against the fixture's fp32 outputs."""
+    from vgen_amd import sketch
+    gen = _gen()
+    pidi, clean = _models(g, dtname, device)
+    o = g["outs"][i]
+    x = gen.inputs(g, i).to(device)
+    mean = torch.tensor(g["mean"], device=device).view(1, -1, 1, 1)
+    std = torch.tensor(g["std"], device=device).view(1, -1, 1, 1)
+    edge = pidi((x - mean) / std)
+    sk = sketch.sketch_condition(x, pidi, clean, g["mean"], g["std"])
+    cl = clean(o["edge16"].float().to(device), flip_in=True, flip_out=True)
+    for t in (edge, sk, cl):
+        assert t.shape == (x.shape[0], 1) + tuple(x.shape[2:]) and t.dtype == torch.float32
+        assert bool(torch.isfinite(t).all()) and float(t.min()) >= 0.0 and float(t.max()) <= 1.0
+    return dict(edge=rel_l2(_sub(edge, g["sub_step"]), o["edge"]), sketch=rel_l2(_sub(sk, g["sub_step"]), o["sketch"]),
+                clean=rel_l2(_sub(cl, g["row_step"]), o["clean"])), (edge, sk)
+
+
+def _check(errs, g, i, dtname, tag):
+    worst = {}
+    for k, e in errs.items():
+        y = g["yardstick"][f"{i}/{k}/{dtname}"]
+        worst[k] = e / y
+        print(f"{tag}/{dtname}/{i}/{k}: err {e:.3e} yardstick {y:.3e} ratio {e / y:.2f}")
+    for k, r in worst.items():
+        assert r <= sc.TOL, (tag, dtname, i, k, errs[k], r)
+    return worst
+
+
+# ---- CPU: structure --------------------------------------------------------------------------------------------------------
+def test_state_dict_keys_and_shapes_are_the_reference_converted_models():
+    from vgen_amd import sketch
+    g = gold("sketch_tiny.pt")
+    with torch.device("meta"):
+        p, c = sketch.pidinet_bsd(), sketch.sketch_simplification_gan()
+    assert {k: tuple(v.shape) for k, v in p.state_dict().items()} == g["shapes"]["pidinet"]
+    assert {k: tuple(v.shape) for k, v in c.state_dict().items()} == g["shapes"]["cleaner"]
+    assert list(p.state_dict()) == list(g["shapes"]["pidinet"]) and list(c.state_dict()) == list(g["shapes"]["cleaner"])
+    assert g["shapes"]["pidinet"]["block1_2.conv1.weight"] == (60, 1, 5, 5) and c.mean == 0.9664114577640158
+    from vgen_amd.synth import seeded_state_dict
+    sd = seeded_state_dict(g["shapes"]["pidinet"], seed=1)
+    p = p.to_empty(device="cpu")
+    p.load_state_dict(sd, strict=True)
+    assert all(torch.equal(v, sd[k]) for k, v in p.state_dict().items())
+
+
+def test_convert_checkpoint_matches_the_stored_digest_of_the_reference_conversion():
+    from vgen_amd import sketch
+    g, gen = gold("sketch_tiny.pt"), _gen()
+    raw = gen.raw_pidinet_state(g["shapes"]["pidinet"])
+    keep = {k: v.clone() for k, v in raw.items()}
+    conv = sketch.convert_checkpoint(raw, config="carv4")
+    assert all(torch.equal(raw[k], keep[k]) for k in raw)                     # the input is left alone
+    assert {k[len("module."):]: tuple(v.shape) for k, v in conv.items()} == g["shapes"]["pidinet"]
+    assert gen.digest(conv) == g["convert_sha256"]
+    with pytest.raises(NotImplementedError, match="config"):
+        sketch.convert_checkpoint(raw, config="cvvv4")
+
+
+@pytest.mark.reference
+def test_convert_checkpoint_against_the_reference_bit_for_bit():
+    from vgen_amd import sketch
+    g, gen = gold("sketch_tiny.pt"), _gen()
+    raw = gen.raw_pidinet_state(g["shapes"]["pidinet"], seed=12)
+    ref = gen._load("pidinet").convert_pidinet({k: v.clone() for k, v in raw.items()}, "carv4")
+    mine = sketch.convert_checkpoint(raw, "carv4")
+    assert list(ref) == list(mine) and all(torch.equal(ref[k], mine[k]) for k in ref)
+
+
+def test_pretrained_reads_the_reference_checkpoint_files(tmp_path, monkeypatch):
+    from vgen_amd import sketch
+    from vgen_amd.synth import seeded_state_dict
+    g, gen = gold("sketch_tiny.pt"), _gen()
+    (tmp_path / "models").mkdir()
+    raw = gen.raw_pidinet_state(g["shapes"]["pidinet"])
+    torch.save({"state_dict": raw, "epoch": 1}, tmp_path / "models" / "table5_pidinet.pth")
+    csd = seeded_state_dict(g["shapes"]["cleaner"], seed=2)
+    torch.save(csd, tmp_path / "models" / "sketch_simplification_gan.pth")
+    monkeypatch.chdir(tmp_path)
+    p = sketch.pidinet_bsd(pretrained=True, vanilla_cnn=True)
+    conv = sketch.convert_checkpoint(raw)
+    assert all(torch.equal(v, conv["module." + k]) for k, v in p.state_dict().items())
+    c = sketch.sketch_simplification_gan(pretrained=True)
+    assert all(torch.equal(v, csd[k]) for k, v in c.state_dict().items())
+
+
+def test_vanilla_cnn_false_is_rejected_by_keyword():
+    from vgen_amd import sketch
+    with pytest.raises(NotImplementedError, match="vanilla_cnn"):
+        sketch.pidinet_bsd(vanilla_cnn=False)
+
+
+@pytest.mark.parametrize("shape", [(1, 3, 36, 64), (1, 3, 64, 60), (1, 3, 0, 64), (1, 1, 64, 64)])
+def test_sizes_that_are_no_multiple_of_8_are_rejected_before_anything_is_launched(emu, shape):
+    from vgen_amd import sketch
+    with torch.device("meta"):
+        p, c = sketch.pidinet_bsd(), sketch.sketch_simplification_gan()
+    with pytest.raises(ValueError):
+        p(torch.zeros(shape))
+    with pytest.raises(ValueError):
+        c(torch.zeros((shape[0], 1 if shape[1] == 3 else 3) + shape[2:]))
+    assert emu.calls == []
+
+
+def test_transposed_conv_packing_against_conv_transpose2d_in_fp64():
+    from vgen_amd import sketch
+    g = torch.Generator("cpu").manual_seed(5)
+    Cc, cp = 8, 64
+    wt = torch.randn(Cc, Cc, 4, 4, generator=g, dtype=torch.float64)
+    b = torch.randn(Cc, generator=g, dtype=torch.float64)
+    x = torch.randn(2, Cc, 3, 5, generator=g, dtype=torch.float64)
+    ref = F.conv_transpose2d(x, wt, b, stride=2, padding=1)
+    Wp = sketch.pack_deconv4x4(wt.float(), cp).double()
+    assert Wp.shape == (4 * cp, 9 * cp)
+    xp = torch.zeros(2, cp, 3, 5, dtype=torch.float64)
+    xp[:, :Cc] = x
+    y = F.conv2d(xp, Wp.view(4 * cp, 3, 3, cp).permute(0, 3, 1, 2), padding=1)          # [2, (py, px, co), 3, 5]
+    y = y.view(2, 2, 2, cp, 3, 5).permute(0, 3, 4, 1, 5, 2).reshape(2, cp, 6, 10)[:, :Cc] + b.view(1, -1, 1, 1)
+    assert float((y - ref).abs().max()) <= 1e-6 * float(ref.abs().max())               # the float32 copy of the weights
+    nz = (Wp.view(2, 2, cp, 9, cp)[:, :, :Cc, :, :Cc].abs().sum(dim=(2, 4)) > 0).sum()
+    assert int(nz) == 16                                                                # 16 of 36 (parity, tap) pairs
+
+
+# ---- CPU: the tiny fixture on the emulator -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtname", ["fp16", "bf16"])
+def test_tiny_fixture_on_the_emulator_within_the_tolerance(emu, dtname):
+    g = gold("sketch_tiny.pt")
+    for i in range(2):
+        errs, (edge, sk) = _fixture_errs(g, i, dtname)
+        _check(errs, g, i, dtname, "emu_tiny")
+        assert rel_l2(sk[0], sk[1]) > 0.1                          # the two inputs of a batch give different sketches
+    assert set(emu.calls) == {"tapgemm", "im2col3x3_small", "sketch_stem", "relu_shuffle16", "sketch_head", "dwconv_relu",
+                              "cdcm_head", "pidinet_emap", "pidinet_fuse"}
+
+
+def test_sketch_condition_equals_the_two_call_form_and_launches_nothing_else(emu):
+    from vgen_amd import sketch
+    g = gold("sketch_tiny.pt")
+    pidi, clean = _models(g, "fp16")
+    x = _gen().inputs(g, 0)
+    mean, std = torch.tensor(g["mean"]).view(1, -1, 1, 1), torch.tensor(g["std"]).view(1, -1, 1, 1)
+    edge = pidi(x.sub(mean).div_(std))
+    n1 = len(emu.calls)
+    two = 1.0 - clean(1.0 - edge)
+    n2 = len(emu.calls)
+    one = sketch.sketch_condition(x, pidi, clean, mean, std)
+    assert emu.calls[n2:] == emu.calls[:n2]                       # the same launches as the two nets, nothing in between
+    # the folded form differs from the composed one only by the fp32 roundings of the two `1 - .` it moves into the kernels
+    assert rel_l2(one, two) < 1e-4, rel_l2(one, two)
+    assert rel_l2(one, g["outs"][0]["sketch"]) <= sc.TOL * g["yardstick"]["0/sketch/fp16"]
+
+
+def test_install_rebinds_the_factories_where_the_engines_hold_them(monkeypatch):
+    from vgen_amd import sketch
+    assert sketch.install() == [] or "tools.annotator.sketch" in sys.modules     # absent package: nothing happens
+    stock_p, stock_c = (lambda **k: "stock pidinet"), (lambda **k: "stock cleaner")
+    tools, ann, pkg = types.ModuleType("tools"), types.ModuleType("tools.annotator"), types.ModuleType("tools.annotator.sketch")
+    inf, eng, other = types.ModuleType("tools.inferences"), types.ModuleType("tools.inferences.engine_a"), types.ModuleType("tools.inferences.engine_b")
+    for m in (tools, ann, pkg, inf):
+        m.__path__ = []
+    pkg.pidinet_bsd, pkg.sketch_simplification_gan = stock_p, stock_c
+    eng.pidinet_bsd, eng.sketch_simplification_gan = stock_p, stock_c
+    other.something_else = 1
+    for m in (tools, ann, pkg, inf, eng, other):
+        monkeypatch.setitem(sys.modules, m.__name__, m)
+    done = sketch.install()
+    assert sorted(done) == sorted([("tools.annotator.sketch", "pidinet_bsd"), ("tools.annotator.sketch", "sketch_simplification_gan"),
+                                   ("tools.inferences.engine_a", "pidinet_bsd"), ("tools.inferences.engine_a", "sketch_simplification_gan")])
+    assert eng.pidinet_bsd is sketch.pidinet_bsd and pkg.sketch_simplification_gan is sketch.sketch_simplification_gan
+    assert not hasattr(other, "pidinet_bsd")
+    import vgen_amd.registry as reg
+    assert "sketch" not in "".join(c.__module__ for cl in reg._native_classes().values() for c in cl)   # registry.install() as it was
+
+
+# ---- CPU: the bounds hold for a CPU model of each kernel -------------------------------------------------------------------
+@pytest.mark.parametrize("dtname", ["fp16", "bf16"])
+def test_the_kernel_bounds_pass_the_fp32_model_and_catch_modelled_mistakes(dtname):
+    dt, be = sc.dt_of(dtname), EmuSketch()
+    x, w = sc.dw_operands(2, 10, 18, 64, 3)
+    lo, hi, xp = sc.dw_reference(x, w, 2, 10, 18, 3, dt, True)
+    p32, p16, y = be.dwconv_relu(x, 2, 10, 18, w, 3, dt, pool=True)
+    assert sc.inside(y, lo, hi) == 0 and torch.equal(p32.double(), xp) and torch.equal(p16, xp.float().to(dt))
+    assert sc.inside(torch.roll(y, 1, 0), lo, hi) > 0                                  # rows shifted by one pixel
+    op = sc.cdcm_operands(2, 20, 36, dt)
+    ref, bound = sc.cdcm_reference(op)
+    out = be.cdcm_head(op["t"], 2, 20, 36, op["Wd"], op["Wa"], op["ba"], op["wr"])[:, :5]
+    assert sc.worst(out, ref, bound) <= 1.0
+    swapped = dict(op, Wd=op["Wd"][[1, 0, 2, 3]].contiguous())                       # two dilations exchanged
+    assert sc.worst(be.cdcm_head(swapped["t"], 2, 20, 36, swapped["Wd"], op["Wa"], op["ba"], op["wr"])[:, :5], ref, bound) > 100
+    mr, w2, br = sc.emap_operands(2, 5, 9)
+    ref, bound = sc.emap_reference(mr, w2, br, 2, 5, 9)
+    assert sc.worst(be.pidinet_emap(mr, 2, 5, 9, w2, br), ref, bound) <= 1.0
+    es, wc, bc = sc.fuse_operands(2, 40, 72)
+    ref, bound = sc.fuse_reference(es, wc, bc, 40, 72)
+    assert sc.worst(be.pidinet_fuse(es, 2, 40, 72, wc, bc), ref, bound) <= 1.0
+    near = torch.sigmoid(bc + sum(wc[i] * F.interpolate(es[i][:, None], (40, 72), mode="nearest") for i in range(4)))
+    assert sc.worst(near, ref, bound) > 100
+    xs, ws, bs, mean, std = sc.stem_operands(2, 16, 24)
+    for flip in (0, 1):
+        lo, hi = sc.stem_reference(xs, ws, bs, mean, std, flip, dt)
+        assert sc.inside(be.sketch_stem(xs, flip, mean, std, ws, bs, dt), lo, hi) == 0
+    assert sc.inside(be.sketch_stem(xs, 0, mean, std, ws, bs, dt), lo, hi) > 0         # the flip forgotten
+    a, wh, bh = sc.head_operands(2, 16, 24, dt)
+    for flip in (0, 1):
+        ref, bound = sc.head_reference(a, wh, bh, 2, 16, 24, flip)
+        assert sc.worst(be.sketch_head(a, 2, 16, 24, 24, wh, bh, flip), ref, bound) <= 1.0
+
+
+# ---- CPU: ABI contract -------------------------------------------------------------------------------------------------------
+FAKE = 0x7f0000001000            # aligned, never dereferenced: every call below returns from the argument checks
+P = [FAKE + (i << 24) for i in range(8)]
+ENTRY = {
+    "vgen_sketch_stem": (["x", "n", "H", "W", "flip", "mean", "stdv", "w", "b", "out", "ldo", "dtype"],
+                         dict(x=P[0], n=2, H=16, W=24, flip=1, mean=0.9, stdv=0.1, w=P[1], b=P[2], out=P[3], ldo=64, dtype=1)),
+    "vgen_relu_shuffle16": (["in_", "ldi", "M", "C", "g", "Hin", "Win", "out", "ldo", "dtype"],
+                            dict(in_=P[0], ldi=256, M=96, C=64, g=2, Hin=6, Win=8, out=P[1], ldo=64, dtype=0)),
+    "vgen_sketch_head": (["a", "lda", "n", "H", "W", "C", "w", "bias", "flip", "out", "dtype"],
+                         dict(a=P[0], lda=64, n=2, H=16, W=24, C=24, w=P[1], bias=0.1, flip=1, out=P[2], dtype=1)),
+    "vgen_dwconv_relu": (["x", "ldx", "n", "H", "W", "Cp", "w", "k", "pool", "xp", "xp16", "y", "dtype"],
+                         dict(x=P[0], ldx=64, n=2, H=10, W=18, Cp=64, w=P[1], k=3, pool=1, xp=P[2], xp16=P[3], y=P[4], dtype=1)),
+    "vgen_cdcm_head": (["t", "ldt", "n", "H", "W", "Wd", "Wa", "ba", "wr", "out", "ldo", "dtype"],
+                       dict(t=P[0], ldt=32, n=2, H=5, W=9, Wd=P[1], Wa=P[2], ba=P[3], wr=P[4], out=P[5], ldo=8, dtype=1)),
+    "vgen_pidinet_emap": (["mr", "ld", "n", "H", "W", "w2", "br", "e"],
+                          dict(mr=P[0], ld=8, n=2, H=5, W=9, w2=P[1], br=0.1, e=P[2])),
+    "vgen_pidinet_fuse": (["e0", "e1", "e2", "e3", "n", "H", "W", "wc0", "wc1", "wc2", "wc3", "bc", "out"],
+                          dict(e0=P[0], e1=P[1], e2=P[2], e3=P[3], n=2, H=40, W=72, wc0=.25, wc1=.25, wc2=.25, wc3=.25, bc=0., out=P[4])),
+}
+NAN = float("nan")
+BAD = [
+    ("vgen_sketch_stem", "null x", dict(x=None), "non-null"), ("vgen_sketch_stem", "null out", dict(out=None), "non-null"),
+    ("vgen_sketch_stem", "odd H", dict(H=15), "even"), ("vgen_sketch_stem", "W 0", dict(W=0), "even"),
+    ("vgen_sketch_stem", "negative n", dict(n=-1), "n >= 0"), ("vgen_sketch_stem", "too many pixels", dict(n=1 << 22, H=32, W=32), "2^31"),
+    ("vgen_sketch_stem", "flip 2", dict(flip=2), "flip"), ("vgen_sketch_stem", "std 0", dict(stdv=0.0), "std"),
+    ("vgen_sketch_stem", "std nan", dict(stdv=NAN), "std"), ("vgen_sketch_stem", "mean nan", dict(mean=NAN), "std"),
+    ("vgen_sketch_stem", "ldo < 64", dict(ldo=48), "ldo"), ("vgen_sketch_stem", "ldo % 8", dict(ldo=68), "ldo"),
+    ("vgen_sketch_stem", "out misaligned", dict(out=P[3] + 8), "aligned"), ("vgen_sketch_stem", "x misaligned", dict(x=P[0] + 2), "aligned"),
+    ("vgen_sketch_stem", "dtype f32", dict(dtype=2), "dtype"),
+    ("vgen_relu_shuffle16", "null in", dict(in_=None), "non-null"), ("vgen_relu_shuffle16", "g 3", dict(g=3), "1 or 2"),
+    ("vgen_relu_shuffle16", "C % 8", dict(C=60), "multiple of 8"), ("vgen_relu_shuffle16", "ldi < 4 C", dict(ldi=128), "row strides"),
+    ("vgen_relu_shuffle16", "ldo < C", dict(ldo=56), "row strides"), ("vgen_relu_shuffle16", "ldo % 8", dict(ldo=68), "row strides"),
+    ("vgen_relu_shuffle16", "ragged images", dict(M=95), "whole"), ("vgen_relu_shuffle16", "Hin 0", dict(Hin=0), "whole"),
+    ("vgen_relu_shuffle16", "misaligned", dict(out=P[1] + 4), "aligned"), ("vgen_relu_shuffle16", "dtype", dict(dtype=2), "dtype"),
+    ("vgen_relu_shuffle16", "g = 2 in place", dict(out=P[0]), "overlaps"),
+    ("vgen_relu_shuffle16", "g = 1 shifted alias", dict(g=1, ldi=64, out=P[0] + 64 * 2 * 3), "overlaps"),
+    ("vgen_relu_shuffle16", "g = 1 alias, other stride", dict(g=1, ldi=128, out=P[0]), "overlaps"),
+    ("vgen_sketch_head", "null w", dict(w=None), "non-null"), ("vgen_sketch_head", "C % 8", dict(C=20), "multiple of 8"),
+    ("vgen_sketch_head", "C > 64", dict(C=72, lda=72), "64"), ("vgen_sketch_head", "lda < C", dict(lda=16), "lda"),
+    ("vgen_sketch_head", "H 0", dict(H=0), "H, W > 0"), ("vgen_sketch_head", "flip", dict(flip=-1), "flip"),
+    ("vgen_sketch_head", "bias nan", dict(bias=NAN), "NaN"), ("vgen_sketch_head", "a misaligned", dict(a=P[0] + 8), "aligned"),
+    ("vgen_sketch_head", "dtype", dict(dtype=3), "dtype"),
+    ("vgen_dwconv_relu", "null y", dict(y=None), "non-null"), ("vgen_dwconv_relu", "k 4", dict(k=4), "1, 3 or 5"),
+    ("vgen_dwconv_relu", "k 1 with w", dict(k=1), "NULL for k = 1"), ("vgen_dwconv_relu", "k 3 without w", dict(w=None), "NULL for k = 1"),
+    ("vgen_dwconv_relu", "Cp % 64", dict(Cp=60, ldx=60), "multiple of 64"), ("vgen_dwconv_relu", "ldx < Cp", dict(ldx=32), "ldx"),
+    ("vgen_dwconv_relu", "pool 2", dict(pool=2), "pool"), ("vgen_dwconv_relu", "pool without xp", dict(xp=None), "pool = 1 needs"),
+    ("vgen_dwconv_relu", "pool odd H", dict(H=9), "pool = 1 needs"), ("vgen_dwconv_relu", "xp without pool", dict(pool=0), "must be NULL"),
+    ("vgen_dwconv_relu", "x misaligned", dict(x=P[0] + 4), "aligned"), ("vgen_dwconv_relu", "dtype", dict(dtype=2), "dtype"),
+    ("vgen_dwconv_relu", "W 0", dict(W=0), "H, W > 0"),
+    ("vgen_cdcm_head", "null Wd", dict(Wd=None), "non-null"), ("vgen_cdcm_head", "null ba", dict(ba=None), "non-null"),
+    ("vgen_cdcm_head", "ldt < 32", dict(ldt=24), "ldt"), ("vgen_cdcm_head", "ldt % 8", dict(ldt=36), "ldt"),
+    ("vgen_cdcm_head", "ldo < 5", dict(ldo=4), "ldo"), ("vgen_cdcm_head", "ldo % 4", dict(ldo=6), "ldo"),
+    ("vgen_cdcm_head", "H 0", dict(H=0), "H, W > 0"), ("vgen_cdcm_head", "t misaligned", dict(t=P[0] + 8), "aligned"),
+    ("vgen_cdcm_head", "out misaligned", dict(out=P[5] + 4), "aligned"), ("vgen_cdcm_head", "dtype", dict(dtype=2), "dtype"),
+    ("vgen_pidinet_emap", "null e", dict(e=None), "non-null"), ("vgen_pidinet_emap", "ld < 5", dict(ld=4), "ld ="),
+    ("vgen_pidinet_emap", "br nan", dict(br=NAN), "NaN"), ("vgen_pidinet_emap", "mr misaligned", dict(mr=P[0] + 4), "aligned"),
+    ("vgen_pidinet_emap", "negative n", dict(n=-2), "n >= 0"),
+    ("vgen_pidinet_fuse", "null e2", dict(e2=None), "non-null"), ("vgen_pidinet_fuse", "H % 8", dict(H=36), "multiples of 8"),
+    ("vgen_pidinet_fuse", "W 0", dict(W=0), "multiples of 8"), ("vgen_pidinet_fuse", "wc nan", dict(wc2=NAN), "NaN"),
+    ("vgen_pidinet_fuse", "out misaligned", dict(out=P[4] + 2), "aligned"),
+]
+
+
+@pytest.mark.parametrize("fn,name,change,needle", BAD, ids=[f"{b[0][5:]}-{b[1]}" for b in BAD])
+def test_new_entry_points_reject_bad_arguments_before_launching(fn, name, change, needle):
+    from vgen_amd import lib
+    l = lib.load()
+    order, good = ENTRY[fn]
+    a = dict(good, **change)
+    rc = getattr(l, fn)(*[a[k] for k in order], None)
+    assert rc == VGEN_E_BADARG, (fn, name, rc)
+    assert needle in l.vgen_last_error().decode(), (fn, name, l.vgen_last_error())
+
+
+def test_abi_version_stays_7_and_the_header_declares_what_the_binding_lists():
+    from vgen_amd import build, lib
+    assert lib.ABI_VERSION == 7 and lib.load().vgen_version() == 7 and "sketch.hip" in build.SOURCES
+    hdr = open(os.path.join(ROOT, "include", "vgen_hip.h")).read()
+    assert "#define VGEN_ABI_VERSION 7" in hdr
+    for fn in ENTRY:
+        decl = re.search(r"int %s\(([^;]*)\);" % fn, hdr).group(1)
+        kinds = []
+        for p in decl.split(","):
+            p = " ".join(p.split())
+            kinds.append(C.c_void_p if "*" in p else {"int64_t": C.c_int64, "int32_t": C.c_int32, "float": C.c_float}[p.split()[0]])
+        res, args = lib.SYMBOLS[fn]
+        assert res is C.c_int and args == kinds, fn
+    for cite in ("sketch_simplification.py:27-73", "pidinet.py:527-704", "inference_tft2v_vcomposer_entrance.py:416"):
+        assert cite in hdr, cite
+
+
+def test_sketch_kernels_compile_without_spills(tmp_path):
+    """Every kernel of sketch.hip by name: zero VGPR / SGPR spills, no scratch, 256-thread blocks."""
+    from vgen_amd import build as b
+    out = tmp_path / "sketch.s"
+    flags = [f for f in b.FLAGS if f != "-fPIC"]
+    r = subprocess.run([b._hipcc()] + flags + ["-S", "--cuda-device-only", os.path.join(b.CSRC, "sketch.hip"), "-o", str(out)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    metas = re.split(r"\n\s+- \.agpr_count:", out.read_text())[1:]
+    want = {"sketch_stem_kernel": 2, "relu_shuffle16_kernel": 2, "sketch_head_kernel": 2, "pool2x2_kernel": 2,
+            "dwconv_relu_kernel": 6, "cdcm_head_kernel": 2, "pidinet_emap_kernel": 1, "pidinet_fuse_kernel": 1}
+    seen = {k: 0 for k in want}
+    for m in metas:
+        name = re.search(r"\.name:\s+(\S+)", m).group(1)
+        for k in want:
+            if k in name:
+                seen[k] += 1
+        for key in ("vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size"):
+            assert int(re.search(r"\.%s:\s+(\d+)" % key, m).group(1)) == 0, (name, key)
+        assert int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", m).group(1)) == 256, name
+    assert seen == want and len(metas) == sum(want.values())
+
+
+# ---- GPU: kernels -------------------------------------------------------------------------------------------------------------
+def _record(key, val):
+    from test_gpu_model import _record as record          # the suite's parity log (same file, same idiom)
+    record(key, val)
+
+
+SENT = -1.2345e33
+
+
+def _canary(shape, dtype):
+    return torch.full(shape, SENT if dtype == torch.float32 else -7.0, dtype=dtype, device=DEV)
+
+
+def _clean(t):
+    return bool((t == (SENT if t.dtype == torch.float32 else -7.0)).all())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtname", ["fp16", "bf16"])
+@pytest.mark.parametrize("k,Cp", [(3, 64), (5, 128), (3, 128), (5, 64)])
+def test_dwconv_relu_per_element_against_fp64(hip_backend, dtname, k, Cp):
+    dt = sc.dt_of(dtname)
+    for (n, H, W), pool in (((2, 5, 9), False), ((2, 20, 36), False), ((2, 10, 18), True)):
+        x, w = sc.dw_operands(n, H, W, Cp, k)
+        lo, hi, xp = sc.dw_reference(x, w, n, H, W, k, dt, pool)
+        got = hip_backend.dwconv_relu(x.to(DEV), n, H, W, w.to(DEV), k, dt, pool=pool)
+        if pool:
+            p32, p16, y = got
+            assert torch.equal(p32.cpu().double(), xp) and torch.equal(p16.cpu(), xp.float().to(dt))
+        else:
+            y = got
+        assert sc.inside(y, lo, hi) == 0, (n, H, W, pool)
+    x, _ = sc.dw_operands(2, 5, 9, Cp, 1)                                  # k = 1: the plain ReLU-cast
+    y = hip_backend.dwconv_relu(x.to(DEV), 2, 5, 9, None, 1, dt)
+    assert torch.equal(y.cpu(), torch.relu(x).to(dt))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtname", ["fp16", "bf16"])
+@pytest.mark.parametrize("hw", [(5, 9), (20, 36), (23, 37)], ids=lambda s: "x".join(map(str, s)))
+def test_cdcm_head_per_element_against_fp64(hip_backend, dtname, hw):
+    dt = sc.dt_of(dtname)
+    H, W = hw
+    op = sc.cdcm_operands(2, H, W, dt)
+    ref, bound = sc.cdcm_reference(op)
+    d = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in op.items()}
+    buf = _canary((2 * H * W + 4, 8), torch.float32)
+    out = hip_backend.cdcm_head(d["t"], 2, H, W, d["Wd"], d["Wa"], d["ba"], d["wr"], out=buf[2:-2])
+    torch.cuda.synchronize()
+    assert _clean(buf[:2]) and _clean(buf[-2:]) and _clean(buf[:, 5:])
+    w = sc.worst(out[:, :5], ref, bound)
+    print(f"cdcm_head/{dtname}/{H}x{W}: worst |err| / bound = {w:.3f}, rel-L2 {rel_l2(out[:, :5], ref):.2e}")
+    _record(f"cdcm_head_bound/{dtname}/{H}x{W}", round(w, 4))
+    assert w <= 1.0
+
+
+@pytest.mark.gpu
+def test_pidinet_emap_and_fuse_per_element_against_fp64(hip_backend):
+    worst = {}
+    for (H, W) in ((40, 72), (20, 36), (10, 18), (5, 9)):
+        mr, w2, br = sc.emap_operands(2, H, W)
+        ref, bound = sc.emap_reference(mr, w2, br, 2, H, W)
+        e = hip_backend.pidinet_emap(mr.to(DEV), 2, H, W, w2.to(DEV), br)
+        worst[f"emap/{H}x{W}"] = sc.worst(e, ref, bound)
+    es, wc, bc = sc.fuse_operands(2, 40, 72)
+    ref, bound = sc.fuse_reference(es, wc, bc, 40, 72)
+    out = hip_backend.pidinet_fuse([e.to(DEV) for e in es], 2, 40, 72, wc, bc)
+    worst["fuse/40x72"] = sc.worst(out, ref, bound)
+    print({k: round(v, 3) for k, v in worst.items()})
+    _record("pidinet_fuse_bound", {k: round(v, 4) for k, v in worst.items()})
+    assert max(worst.values()) <= 1.0, worst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtname", ["fp16", "bf16"])
+def test_sketch_stem_and_head_per_element_against_fp64(hip_backend, dtname):
+    dt = sc.dt_of(dtname)
+    n, H, W = 2, 16, 24
+    xs, ws, bs, mean, std = sc.stem_operands(n, H, W)
+    a, wh, bh = sc.head_operands(n, H, W, dt)
+    for flip in (0, 1):
+        lo, hi = sc.stem_reference(xs, ws, bs, mean, std, flip, dt)
+        y = hip_backend.sketch_stem(xs.to(DEV), flip, mean, std, ws.to(DEV), bs.to(DEV), dt)
+        assert y.shape == (n * H * W // 4, 64) and sc.inside(y, lo, hi) == 0 and not bool(y[:, 48:].any())
+        ref, bound = sc.head_reference(a, wh, bh, n, H, W, flip)
+        o = hip_backend.sketch_head(a.to(DEV), n, H, W, 24, wh.to(DEV), bh, flip)
+        w = sc.worst(o, ref, bound)
+        _record(f"sketch_head_bound/{dtname}/flip{flip}", round(w, 4))
+        assert o.shape == (n, 1, H, W) and w <= 1.0, w
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtname", ["fp16", "bf16"])
+def test_relu_shuffle16_is_bit_exact_against_pixel_shuffle(hip_backend, dtname):
+    dt = sc.dt_of(dtname)
+    g = torch.Generator("cpu").manual_seed(3)
+    n, Hin, Win, Cc = 2, 5, 9, 64
+    a = torch.randn(n * Hin * Win, 4 * Cc + 8, generator=g).to(dt)
+    a[0, 0], a[1, 1], a[2, 2], a[3, 3] = float("-inf"), float("inf"), -0.0, float("nan")
+    ref = sc.shuffle_reference(a, Cc, 2, n, Hin, Win)
+    buf = _canary((4 * n * Hin * Win + 6, Cc + 8), dt)
+    out = hip_backend.relu_shuffle16(a.to(DEV)[:, : 4 * Cc], Cc, 2, Hin, Win, out=buf[3:-3, :Cc])
+    torch.cuda.synchronize()
+    assert _clean(buf[:3]) and _clean(buf[-3:]) and _clean(buf[:, Cc:])
+    ok = ~torch.isnan(ref)                                                  # NaN keeps its bits; everything else is equal
+    assert int((~ok).sum()) == 1 and torch.equal(out.cpu()[ok], ref[ok]) and bool(torch.isnan(out.cpu()[~ok]).all())
+    assert not bool((out.cpu().view(torch.int16)[ok] < 0).any())            # no negative zero either
+    b = a.to(DEV).clone()
+    one = hip_backend.relu_shuffle16(b[:, :Cc], Cc)                          # g = 1, in place, on a column view
+    assert one.data_ptr() == b.data_ptr() and torch.equal(b[:, Cc:].cpu(), a[:, Cc:])
+    r1 = torch.relu(a[:, :Cc].float()).to(dt)
+    ok = ~torch.isnan(r1)
+    assert torch.equal(b[:, :Cc].cpu()[ok], r1[ok]) and bool(torch.isnan(b[:, :Cc].cpu()[~ok]).all())
+
+
+@pytest.mark.gpu
+def test_every_launch_leaves_the_rows_and_columns_around_its_outputs_untouched(hip_backend):
+    """Raw entry points with every output inside a larger canary-filled allocation (odd sizes, ragged tiles)."""
+    l, dt = hip_backend.lib, torch.float16
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    n, H, W = 2, 10, 18
+    # stem: rows [n H/2 W/2, 64] inside [.. + 4, 72]
+    xs, ws, bs, mean, std = sc.stem_operands(n, H, W)
+    buf = _canary((n * H * W // 4 + 4, 72), dt)
+    assert l.vgen_sketch_stem(ptr(xs.to(DEV)), n, H, W, 1, mean, std, ptr(ws.to(DEV)), ptr(bs.to(DEV)), ptr(buf[2:]), 72, 1, st) == 0
+    torch.cuda.synchronize()
+    assert _clean(buf[:2]) and _clean(buf[-2:]) and _clean(buf[:, 64:]) and not _clean(buf[2:-2, :48])
+    # head: image [n, 1, H, W] inside a flat buffer
+    a, wh, bh = sc.head_operands(n, H, W, dt)
+    flat = _canary((n * H * W + 64,), torch.float32)
+    assert l.vgen_sketch_head(ptr(a.to(DEV)), 64, n, H, W, 24, ptr(wh.to(DEV)), bh, 0, ptr(flat[32:]), 1, st) == 0
+    torch.cuda.synchronize()
+    assert _clean(flat[:32]) and _clean(flat[-32:]) and float(flat[32:-32].min()) >= 0
+    # dwconv with pool: three outputs, each with guard rows; 9 x 5 pooled pixels = ragged pixel groups
+    x, w = sc.dw_operands(n, H, W, 64, 5)
+    M = n * H * W // 4
+    xb = torch.full((n * H * W + 2, 72), float("nan"), device=DEV)
+    xb[1:-1, :64] = x.to(DEV)
+    y, p32, p16 = _canary((M + 4, 64), dt), _canary((M + 4, 64), torch.float32), _canary((M + 4, 64), dt)
+    assert l.vgen_dwconv_relu(ptr(xb[1:]), 72, n, H, W, 64, ptr(w.to(DEV)), 5, 1, ptr(p32[2:]), ptr(p16[2:]), ptr(y[2:]), 1, st) == 0
+    torch.cuda.synchronize()
+    for t in (y, p32, p16):
+        assert _clean(t[:2]) and _clean(t[-2:]) and bool(torch.isfinite(t[2:-2].float()).all())
+    # emap / fuse: maps inside flat buffers
+    mr, w2, br = sc.emap_operands(n, 5, 9)
+    flat = _canary((n * 45 + 16,), torch.float32)
+    assert l.vgen_pidinet_emap(ptr(mr.to(DEV)), 8, n, 5, 9, ptr(w2.to(DEV)), br, ptr(flat[8:]), st) == 0
+    es, wc, bc = sc.fuse_operands(n, 40, 72)
+    es = [e.to(DEV) for e in es]
+    fo = _canary((n * 40 * 72 + 16,), torch.float32)
+    assert l.vgen_pidinet_fuse(ptr(es[0]), ptr(es[1]), ptr(es[2]), ptr(es[3]), n, 40, 72, *wc, bc, ptr(fo[8:]), st) == 0
+    torch.cuda.synchronize()
+    assert _clean(flat[:8]) and _clean(flat[-8:]) and _clean(fo[:8]) and _clean(fo[-8:])
+    assert bool(torch.isfinite(flat[8:-8]).all()) and float(fo[8:-8].min()) > 0 and float(fo[8:-8].max()) < 1
+
+
+# ---- GPU: models ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtname", ["fp16", "bf16"])
+def test_tiny_fixture_on_the_device_within_the_tolerance(hip_backend, dtname):
+    g = gold("sketch_tiny.pt")
+    for i in range(2):
+        errs, (edge, sk) = _fixture_errs(g, i, dtname, DEV)
+        worst = _check(errs, g, i, dtname, "gpu_tiny")
+        _record(f"sketch_tiny/{dtname}/{i}", dict(err=errs, ratio={k: round(v, 3) for k, v in worst.items()}))
+        assert rel_l2(sk[0], sk[1]) > 0.1
+
+
+@pytest.mark.gpu
+def test_full_fixture_on_the_device_within_the_tolerance(hip_backend):
+    g = gold("sketch_full.pt")
+    errs, _ = _fixture_errs(g, 0, "fp16", DEV)
+    worst = _check(errs, g, 0, "fp16", "gpu_full")
+    _record("sketch_full/fp16/0", dict(err=errs, ratio={k: round(v, 3) for k, v in worst.items()}))

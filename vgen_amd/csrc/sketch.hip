@@ -1,0 +1,627 @@
+// sketch.hip — the small kernels around the tap-GEMMs of the sketch-simplification net (tools/annotator/sketch/
+// sketch_simplification.py:27-73, called at tools/inferences/inference_tft2v_vcomposer_entrance.py:417 as
+// `sketch = 1.0 - cleaner(1.0 - sketch)`).  Every dense 3x3 conv of that net (and each ConvTranspose2d, as ONE 3x3 conv
+// with 4 C output columns) is a vgen_tapgemm launch with a 16-bit output; what the tap-GEMM cannot express lives here:
+//
+//   vgen_sketch_stem     [1 - x], (. - mean) / std, Conv2d(1, 48, 5, 2, 2) + bias + ReLU -> 16-bit rows [n H/2 W/2, 64]
+//   vgen_relu_shuffle16  ReLU on 16-bit rows, optionally with the depth-to-space of a transposed conv's 4 C columns
+//   vgen_sketch_head     Conv2d(24, 1, 3, 1, 1) + bias + sigmoid [, 1 - .] -> fp32 image [n, 1, H, W]
+//
+// All three are streaming kernels: every global access of a 16-bit row is 16 contiguous bytes (8 channels) per lane, the
+// few fp32 weights sit in LDS, out-of-image taps are predicated zeros (never reads), nothing outside the operands' rows /
+// columns is touched, fp32 accumulation runs in ONE fixed order (bias first, then taps row-major, channels ascending, one
+// fmaf each), no scratch.
+#include "common.h"
+
+namespace {
+
+constexpr int SK_CP = 64;        // padded channel count of the cleaner's 48- and 24-channel rows
+
+// ---- stem ----------------------------------------------------------------------------------------------------------------
+// one thread = (output pixel, 8 output channels); the 8 threads of a pixel read the same 25 inputs (one L1 line each row)
+template <typename T>
+__global__ __launch_bounds__(256) void sketch_stem_kernel(const float* __restrict__ x, int64_t npix, int H, int W, int Ho,
+                                                          int Wo, int flip, float mean, float stdv,
+                                                          const float* __restrict__ w, const float* __restrict__ b,
+                                                          uint16_t* __restrict__ out, int64_t ldo) {
+  __shared__ __attribute__((aligned(16))) float ws[25 * SK_CP];
+  __shared__ __attribute__((aligned(16))) float bs[SK_CP];
+  for (int i = threadIdx.x; i < 25 * SK_CP; i += 256) ws[i] = w[i];
+  if (threadIdx.x < SK_CP) bs[threadIdx.x] = b[threadIdx.x];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t m = i >> 3;
+  const int c0 = ((int)i & 7) * 8;
+  if (m >= npix) return;
+  const int64_t hw = (int64_t)Ho * Wo;
+  const int64_t img = m / hw;
+  const int rem = (int)(m - img * hw);
+  const int oy = rem / Wo, ox = rem - oy * Wo;
+  const float* const xi = x + img * (int64_t)H * W;
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = bs[c0 + j];
+#pragma unroll 1                                      // one kernel row at a time: 40 weights live, not 200 (235 -> < 64 VGPRs)
+  for (int ky = 0; ky < 5; ++ky) {
+    const int iy = 2 * oy + ky - 2;
+#pragma unroll
+    for (int kx = 0; kx < 5; ++kx) {
+      const int ix = 2 * ox + kx - 2;
+      float v = 0.f;                                   // the conv pads the NORMALISED image with zeros
+      if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
+        v = xi[(int64_t)iy * W + ix];
+        if (flip) v = 1.0f - v;
+        v = (v - mean) / stdv;
+      }
+      const f32x4 w0 = *(const f32x4*)(ws + (ky * 5 + kx) * SK_CP + c0);
+      const f32x4 w1 = *(const f32x4*)(ws + (ky * 5 + kx) * SK_CP + c0 + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc[j] = fmaf(w0[j], v, acc[j]);
+        acc[4 + j] = fmaf(w1[j], v, acc[4 + j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = fmaxf(acc[j], 0.f);
+  u32x4 o;
+  o.x = pack2<T>(acc[0], acc[1]);
+  o.y = pack2<T>(acc[2], acc[3]);
+  o.z = pack2<T>(acc[4], acc[5]);
+  o.w = pack2<T>(acc[6], acc[7]);
+  *(u32x4*)(out + m * ldo + c0) = o;
+}
+
+// ---- ReLU (+ depth-to-space) on 16-bit rows --------------------------------------------------------------------------------
+// INF = the format's +inf bit pattern: a negative non-NaN value becomes +0, everything else keeps its bits
+template <uint32_t INF>
+__device__ __forceinline__ uint32_t relu16x2(uint32_t v) {
+  const uint32_t lo = v & 0xffffu, hi = v >> 16;
+  const uint32_t rl = ((lo & 0x8000u) && (lo & 0x7fffu) <= INF) ? 0u : lo;
+  const uint32_t rh = ((hi & 0x8000u) && (hi & 0x7fffu) <= INF) ? 0u : hi;
+  return rl | (rh << 16);
+}
+
+template <uint32_t INF>
+__global__ __launch_bounds__(256) void relu_shuffle16_kernel(const uint16_t* in, int64_t ldi, int64_t total, int C8, int g,
+                                                             int Hin, int Win, uint16_t* out, int64_t ldo) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int gg = g * g;
+  const int c8 = (int)(i % C8);
+  const int64_t t = i / C8;
+  const int q = (int)(t % gg);
+  const int64_t m = t / gg;
+  u32x4 v = *(const u32x4*)(in + m * ldi + ((int64_t)q * C8 + c8) * 8);
+  v.x = relu16x2<INF>(v.x);
+  v.y = relu16x2<INF>(v.y);
+  v.z = relu16x2<INF>(v.z);
+  v.w = relu16x2<INF>(v.w);
+  int64_t orow = m;
+  if (g > 1) {
+    const int64_t hw = (int64_t)Hin * Win;
+    const int64_t img = m / hw;
+    const int rem = (int)(m - img * hw);
+    const int y = rem / Win, xx = rem - y * Win;
+    const int py = q / g, px = q - py * g;
+    orow = (img * (g * Hin) + (g * y + py)) * (int64_t)(g * Win) + (g * xx + px);
+  }
+  *(u32x4*)(out + orow * ldo + c8 * 8) = v;
+}
+
+// ---- head -----------------------------------------------------------------------------------------------------------------
+// one thread = one output pixel: 9 taps x C channels, 16-byte loads of the 16-bit rows
+template <typename T>
+__global__ __launch_bounds__(256) void sketch_head_kernel(const uint16_t* __restrict__ a, int64_t lda, int64_t npix, int H,
+                                                          int W, int C, const float* __restrict__ w, float bias, int flip,
+                                                          float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float ws[9 * SK_CP];
+  for (int i = threadIdx.x; i < 9 * C; i += 256) ws[i] = w[i];
+  __syncthreads();
+  const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (m >= npix) return;
+  const int64_t hw = (int64_t)H * W;
+  const int rem = (int)(m % hw);
+  const int oy = rem / W, ox = rem - oy * W;
+  float acc = bias;
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky) {
+    const int iy = oy + ky - 1;
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int ix = ox + kx - 1;
+      if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
+        const uint16_t* const row = a + (m + (int64_t)(ky - 1) * W + (kx - 1)) * lda;
+        const float* const wt = ws + (ky * 3 + kx) * C;
+        for (int c = 0; c < C; c += 8) {
+          const u32x4 v = *(const u32x4*)(row + c);
+          const uint32_t p[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            acc = fmaf(wt[c + 2 * j], T::to_f32((uint16_t)(p[j] & 0xffffu)), acc);
+            acc = fmaf(wt[c + 2 * j + 1], T::to_f32((uint16_t)(p[j] >> 16)), acc);
+          }
+        }
+      }
+    }
+  }
+  const float s = 1.0f / (1.0f + expf(-acc));
+  out[m] = flip ? 1.0f - s : s;
+}
+
+inline bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+  const uintptr_t ab = (uintptr_t)a, bb = (uintptr_t)b;
+  return !(ab + abytes <= bb || bb + bbytes <= ab);
+}
+
+}  // namespace
+
+extern "C" int vgen_sketch_stem(const float* x, int64_t n, int32_t H, int32_t W, int32_t flip, float mean, float stdv,
+                                const float* w, const float* b, void* out, int64_t ldo, int32_t dtype, void* stream) {
+  VGEN_REQUIRE(dtype == VGEN_BF16 || dtype == VGEN_F16, "sketch_stem: dtype must be VGEN_BF16 or VGEN_F16");
+  VGEN_REQUIRE(x && w && b && out, "sketch_stem: x, w, b and out must be non-null");
+  VGEN_REQUIRE(n >= 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "sketch_stem: n >= 0, H = %d and W = %d must be positive and even",
+               (int)H, (int)W);
+  VGEN_REQUIRE(n * (int64_t)H * W < (1LL << 31), "sketch_stem: n H W must be < 2^31");
+  VGEN_REQUIRE(flip == 0 || flip == 1, "sketch_stem: flip must be 0 or 1");
+  VGEN_REQUIRE(stdv > 0.f && stdv < INFINITY && mean == mean, "sketch_stem: std must be positive and finite, mean not NaN");
+  VGEN_REQUIRE(ldo >= SK_CP && ldo % 8 == 0, "sketch_stem: ldo = %lld must be >= 64 and a multiple of 8", (long long)ldo);
+  VGEN_REQUIRE((((uintptr_t)x) & 3u) == 0 && vgen_aligned16(w) && vgen_aligned16(b) && vgen_aligned16(out),
+               "sketch_stem: x must be 4-byte, w / b / out 16-byte aligned");
+  if (n == 0) return 0;
+  const int Ho = H / 2, Wo = W / 2;
+  const int64_t npix = n * Ho * Wo;
+  const int64_t grid = (npix * 8 + 255) / 256;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == VGEN_BF16)
+    hipLaunchKernelGGL(sketch_stem_kernel<BF16>, dim3((unsigned)grid), dim3(256), 0, s, x, npix, H, W, Ho, Wo, flip, mean, stdv,
+                       w, b, (uint16_t*)out, ldo);
+  else
+    hipLaunchKernelGGL(sketch_stem_kernel<F16>, dim3((unsigned)grid), dim3(256), 0, s, x, npix, H, W, Ho, Wo, flip, mean, stdv,
+                       w, b, (uint16_t*)out, ldo);
+  return vgen_check_launch("sketch_stem");
+}
+
+extern "C" int vgen_relu_shuffle16(const void* in, int64_t ldi, int64_t M, int32_t C, int32_t g, int32_t Hin, int32_t Win,
+                                   void* out, int64_t ldo, int32_t dtype, void* stream) {
+  VGEN_REQUIRE(dtype == VGEN_BF16 || dtype == VGEN_F16, "relu_shuffle16: dtype must be VGEN_BF16 or VGEN_F16");
+  VGEN_REQUIRE(in && out, "relu_shuffle16: in and out must be non-null");
+  VGEN_REQUIRE(g == 1 || g == 2, "relu_shuffle16: g = %d must be 1 or 2", (int)g);
+  VGEN_REQUIRE(C > 0 && C % 8 == 0 && C <= 8192, "relu_shuffle16: C = %d must be a positive multiple of 8, <= 8192", (int)C);
+  VGEN_REQUIRE(M >= 0 && M * g * g < (1LL << 31), "relu_shuffle16: M g^2 must be in [0, 2^31)");
+  VGEN_REQUIRE(ldi >= (int64_t)g * g * C && ldo >= C && ldi % 8 == 0 && ldo % 8 == 0 && ldi < (1LL << 30) && ldo < (1LL << 30),
+               "relu_shuffle16: row strides must cover g^2 C / C columns and be multiples of 8");
+  VGEN_REQUIRE(vgen_aligned16(in) && vgen_aligned16(out), "relu_shuffle16: in and out must be 16-byte aligned");
+  if (g == 2)
+    VGEN_REQUIRE(Hin > 0 && Win > 0 && M % ((int64_t)Hin * Win) == 0, "relu_shuffle16: g = 2 needs M to be whole Hin x Win images");
+  if (M == 0) return 0;
+  if (!(g == 1 && in == out && ldi == ldo)) {
+    // only the exact in-place form of g = 1 may alias (a lane reads its 16 bytes before it writes the same 16 bytes)
+    VGEN_REQUIRE(!ranges_overlap(in, (size_t)((M - 1) * ldi + (int64_t)g * g * C) * 2, out,
+                                 (size_t)((M * g * g - 1) * ldo + C) * 2),
+                 "relu_shuffle16: out overlaps in (only g = 1 with out == in and ldo == ldi may alias)");
+  }
+  const int64_t total = M * g * g * (C / 8);
+  const int64_t grid = (total + 255) / 256;
+  VGEN_REQUIRE(grid < (1LL << 31), "relu_shuffle16: too large");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == VGEN_BF16)
+    hipLaunchKernelGGL(relu_shuffle16_kernel<0x7f80u>, dim3((unsigned)grid), dim3(256), 0, s, (const uint16_t*)in, ldi, total,
+                       C / 8, g, Hin, Win, (uint16_t*)out, ldo);
+  else
+    hipLaunchKernelGGL(relu_shuffle16_kernel<0x7c00u>, dim3((unsigned)grid), dim3(256), 0, s, (const uint16_t*)in, ldi, total,
+                       C / 8, g, Hin, Win, (uint16_t*)out, ldo);
+  return vgen_check_launch("relu_shuffle16");
+}
+
+extern "C" int vgen_sketch_head(const void* a, int64_t lda, int64_t n, int32_t H, int32_t W, int32_t C, const float* w,
+                                float bias, int32_t flip, float* out, int32_t dtype, void* stream) {
+  VGEN_REQUIRE(dtype == VGEN_BF16 || dtype == VGEN_F16, "sketch_head: dtype must be VGEN_BF16 or VGEN_F16");
+  VGEN_REQUIRE(a && w && out, "sketch_head: a, w and out must be non-null");
+  VGEN_REQUIRE(n >= 0 && H > 0 && W > 0 && n * (int64_t)H * W < (1LL << 31), "sketch_head: n >= 0, H, W > 0, n H W < 2^31");
+  VGEN_REQUIRE(C > 0 && C % 8 == 0 && C <= SK_CP, "sketch_head: C = %d must be a positive multiple of 8, <= 64", (int)C);
+  VGEN_REQUIRE(lda >= C && lda % 8 == 0 && lda < (1LL << 30), "sketch_head: lda = %lld must be >= C and a multiple of 8", (long long)lda);
+  VGEN_REQUIRE(flip == 0 || flip == 1, "sketch_head: flip must be 0 or 1");
+  VGEN_REQUIRE(bias == bias, "sketch_head: bias must not be NaN");
+  VGEN_REQUIRE(vgen_aligned16(a) && vgen_aligned16(w) && (((uintptr_t)out) & 3u) == 0,
+               "sketch_head: a / w must be 16-byte, out 4-byte aligned");
+  if (n == 0) return 0;
+  const int64_t npix = n * (int64_t)H * W;
+  const int64_t grid = (npix + 255) / 256;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == VGEN_BF16)
+    hipLaunchKernelGGL(sketch_head_kernel<BF16>, dim3((unsigned)grid), dim3(256), 0, s, (const uint16_t*)a, lda, npix, H, W, C, w,
+                       bias, flip, out);
+  else
+    hipLaunchKernelGGL(sketch_head_kernel<F16>, dim3((unsigned)grid), dim3(256), 0, s, (const uint16_t*)a, lda, npix, H, W, C, w,
+                       bias, flip, out);
+  return vgen_check_launch("sketch_head");
+}
+
+// =============================================================================================================================
+// PiDiNet (tools/annotator/sketch/pidinet.py:527-704, the converted "vanilla CNN" form pidinet_bsd builds: :732-746), called
+// at tools/inferences/inference_tft2v_vcomposer_entrance.py:416.  The 1x1 convs of the trunk (conv2 + the stride-2 blocks'
+// shortcut as a second K segment, :544,538) and of the side heads (CDCM.conv1, :474) run on vgen_tapgemm; here:
+//
+//   vgen_dwconv_relu   [2x2 max-pool,] depthwise k x k conv in fp32, ReLU, 16-bit rows: the A operand of conv2 (:547-551)
+//   vgen_cdcm_head     the four dilated 3x3 convs of CDCM (:475-488) on the matrix units from an LDS-resident haloed tile,
+//                      and the two channel reductions that are all the rest of the side head needs (5 floats per pixel)
+//   vgen_pidinet_emap  CSAM's 3x3 conv + sigmoid (:454-464) and MapReduce (:496-500) on those 5 floats -> one edge map
+//   vgen_pidinet_fuse  bilinear (align_corners = False) resampling of the four maps, classifier, sigmoid (:687-704)
+// =============================================================================================================================
+namespace {
+
+constexpr int DW_PX = 4;         // consecutive output pixels of a row per thread (a k-wide window slides over PX + k - 1 loads)
+
+// 2x2 / stride-2 max-pool of fp32 rows: fp32 rows + their 16-bit cast.  One thread = (output pixel, 4 channels).
+template <typename T>
+__global__ __launch_bounds__(256) void pool2x2_kernel(const float* __restrict__ x, int64_t ldx, int64_t total, int H, int W,
+                                                      int C4, float* __restrict__ xp, uint16_t* __restrict__ xp16) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int c = (int)(i % C4) * 4;
+  const int64_t m = i / C4;
+  const int Ho = H >> 1, Wo = W >> 1;
+  const int64_t hw = (int64_t)Ho * Wo;
+  const int64_t img = m / hw;
+  const int rem = (int)(m - img * hw);
+  const int oy = rem / Wo, ox = rem - oy * Wo;
+  const float* const s = x + ((img * H + 2 * oy) * (int64_t)W + 2 * ox) * ldx + c;
+  const f32x4 a = *(const f32x4*)s, b = *(const f32x4*)(s + ldx);
+  const f32x4 d = *(const f32x4*)(s + (int64_t)W * ldx), e = *(const f32x4*)(s + ((int64_t)W + 1) * ldx);
+  f32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = fmaxf(fmaxf(a[j], b[j]), fmaxf(d[j], e[j]));
+  const int64_t o = m * (int64_t)(C4 * 4) + c;
+  *(f32x4*)(xp + o) = v;
+  *(u32x2*)(xp16 + o) = pack4<T>(v[0], v[1], v[2], v[3]);
+}
+
+// depthwise K x K conv (pad K / 2), fp32, fixed tap order (ky, then kx, one fmaf each from 0), ReLU, 16-bit.
+// One thread = (DW_PX consecutive pixels of one image row, 4 channels): adjacent lanes hold adjacent channel groups, so a
+// pixel's channels are one contiguous run of 16-byte loads; weights [K*K, Cp] come through L1 (the same Cp floats per tap
+// for every pixel).  K = 1 (w = NULL) is the plain ReLU-cast.
+template <typename T, int K>
+__global__ __launch_bounds__(256) void dwconv_relu_kernel(const float* __restrict__ x, int64_t ldx, int64_t total, int H,
+                                                          int W, int C4, const float* __restrict__ w,
+                                                          uint16_t* __restrict__ y) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int Cp = C4 * 4;
+  const int c = (int)(i % C4) * 4;
+  const int64_t t = i / C4;
+  const int gpr = (W + DW_PX - 1) / DW_PX;               // pixel groups per row
+  const int xg = (int)(t % gpr);
+  const int64_t rowi = t / gpr;                          // img * H + y
+  const int oy = (int)(rowi % H);
+  const int x0 = xg * DW_PX;
+  constexpr int R = K / 2;
+  f32x4 acc[DW_PX];
+#pragma unroll
+  for (int p = 0; p < DW_PX; ++p) acc[p] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ky = 0; ky < K; ++ky) {
+    const int iy = oy + ky - R;
+    if (iy < 0 || iy >= H) continue;                     // out-of-image taps are zeros, never reads
+    const float* const srow = x + (rowi + (ky - R)) * (int64_t)W * ldx + c;
+    f32x4 v[DW_PX + K - 1];
+#pragma unroll
+    for (int q = 0; q < DW_PX + K - 1; ++q) {
+      const int ix = x0 + q - R;
+      v[q] = (ix >= 0 && ix < W) ? *(const f32x4*)(srow + (int64_t)ix * ldx) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int kx = 0; kx < K; ++kx) {
+      f32x4 wt = {1.f, 1.f, 1.f, 1.f};
+      if (K > 1) wt = *(const f32x4*)(w + (ky * K + kx) * Cp + c);
+#pragma unroll
+      for (int p = 0; p < DW_PX; ++p)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[p][j] = (K > 1) ? fmaf(wt[j], v[p + kx][j], acc[p][j]) : v[p + kx][j];
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < DW_PX; ++p) {
+    if (x0 + p < W)
+      *(u32x2*)(y + (rowi * W + x0 + p) * (int64_t)Cp + c) =
+          pack4<T>(fmaxf(acc[p][0], 0.f), fmaxf(acc[p][1], 0.f), fmaxf(acc[p][2], 0.f), fmaxf(acc[p][3], 0.f));
+  }
+}
+
+// ---- CDCM head --------------------------------------------------------------------------------------------------------------
+// Block = 256 threads = 4 waves, tile = CD_TH x CD_TW output pixels of one image.  The haloed 16-bit input tile
+// [CD_TH + 22][CD_TW + 22][32 channels] sits in LDS (72 960 B; out-of-image positions are written as zeros, never read from
+// memory).  A wave owns 2 tile rows; one MFMA 16x16x32 = (16 output channels) x (the 16 pixels of a tile row) x (the 32 input
+// channels of ONE tap), operands swapped as in tapgemm.hip (a lane ends up with 4 consecutive channels of one pixel).  36
+// (dilation, tap) pairs x 2 channel fragments x 2 rows = 144 MFMAs per wave; the weight fragments come straight from L2 in
+// operand layout (73 728 B for the whole head, shared by every block).  u stays in fp32 registers; the epilogue reduces it
+// to m[0..3] = Wa . relu(u) + ba and r = wr . u (8 channels per lane, then the 4 lanes of a pixel by two xor-shuffles).
+constexpr int CD_TH = 8, CD_TW = 16, CD_HALO = 11, CD_C = 32;
+constexpr int CD_LH = CD_TH + 2 * CD_HALO, CD_LW = CD_TW + 2 * CD_HALO;
+constexpr int CD_LDS = CD_LH * CD_LW * CD_C * 2;
+
+struct cdcm_params {
+  const uint16_t* t;
+  int64_t ldt;
+  int H, W, tiles_x, tiles_y;
+  const uint16_t* Wd;     // [4][9][32 co][32 ci]
+  const float* Wa;        // [4][32]
+  const float* ba;        // [4]
+  const float* wr;        // [32]
+  float* out;
+  int64_t ldo;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void cdcm_head_kernel(const cdcm_params p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint16_t* const ts = (uint16_t*)smem;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lq = lane >> 4;
+  const int bx = blockIdx.x % p.tiles_x;
+  const int by = (blockIdx.x / p.tiles_x) % p.tiles_y;
+  const int64_t img = blockIdx.x / (p.tiles_x * p.tiles_y);
+  const int ty0 = by * CD_TH, tx0 = bx * CD_TW;
+  const uint16_t* const timg = p.t + img * (int64_t)p.H * p.W * p.ldt;
+
+  for (int i = tid; i < CD_LH * CD_LW * 4; i += 256) {
+    const int pos = i >> 2, ch = (i & 3) * 8;
+    const int ly = pos / CD_LW, lx = pos - ly * CD_LW;
+    const int gy = ty0 - CD_HALO + ly, gx = tx0 - CD_HALO + lx;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) v = *(const u32x4*)(timg + ((int64_t)gy * p.W + gx) * p.ldt + ch);
+    *(u32x4*)(ts + pos * CD_C + ch) = v;
+  }
+  __syncthreads();
+
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int mf = 0; mf < 2; ++mf) acc[mf][0] = acc[mf][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const uint16_t* const wl = p.Wd + lr * CD_C + lq * 8;
+  const uint16_t* const tl = ts + ((wave * 2 + CD_HALO) * CD_LW + lr + CD_HALO) * CD_C + lq * 8;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const int dil = 5 + 2 * d;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      const int dy = (tap / 3 - 1) * dil, dx = (tap % 3 - 1) * dil;
+      const u32x4 a0 = *(const u32x4*)(wl + (d * 9 + tap) * CD_C * CD_C);
+      const u32x4 a1 = *(const u32x4*)(wl + (d * 9 + tap) * CD_C * CD_C + 16 * CD_C);
+#pragma unroll
+      for (int mf = 0; mf < 2; ++mf) {
+        const u32x4 b = *(const u32x4*)(tl + ((mf + dy) * CD_LW + dx) * CD_C);
+        acc[mf][0] = T::mfma32(a0, b, acc[mf][0]);
+        acc[mf][1] = T::mfma32(a1, b, acc[mf][1]);
+      }
+    }
+  }
+
+  // lane (lr, lq): pixel (tile row 2 wave + mf, column lr), channels f * 16 + lq * 4 + 0..3
+  float wa[4][8], wrr[8];
+#pragma unroll
+  for (int f = 0; f < 2; ++f)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int co = f * 16 + lq * 4 + r;
+      wrr[f * 4 + r] = p.wr[co];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) wa[j][f * 4 + r] = p.Wa[j * CD_C + co];
+    }
+#pragma unroll
+  for (int mf = 0; mf < 2; ++mf) {
+    float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float u = acc[mf][f][r];
+        const float ur = fmaxf(u, 0.f);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = fmaf(wa[j][f * 4 + r], ur, s[j]);
+        s[4] = fmaf(wrr[f * 4 + r], u, s[4]);
+      }
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      s[j] += __shfl_xor(s[j], 16, 64);
+      s[j] += __shfl_xor(s[j], 32, 64);
+    }
+    const int gy = ty0 + wave * 2 + mf, gx = tx0 + lr;
+    if (lq == 0 && gy < p.H && gx < p.W) {
+      float* const o = p.out + ((img * p.H + gy) * (int64_t)p.W + gx) * p.ldo;
+      *(f32x4*)o = f32x4{s[0] + p.ba[0], s[1] + p.ba[1], s[2] + p.ba[2], s[3] + p.ba[3]};
+      o[4] = s[4];
+    }
+  }
+}
+
+// e[pix] = sigmoid( sum_{tap, j} w2[tap][j] m_j[neighbour] ) * r[pix] + br;  m is zero outside the image (the conv pads m,
+// bias included, with zeros).  One thread = one pixel.
+__global__ __launch_bounds__(256) void pidinet_emap_kernel(const float* __restrict__ mr, int64_t ld, int64_t npix, int H, int W,
+                                                           const float* __restrict__ w2, float br, float* __restrict__ e) {
+  const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (m >= npix) return;
+  const int64_t hw = (int64_t)H * W;
+  const int rem = (int)(m % hw);
+  const int oy = rem / W, ox = rem - oy * W;
+  float acc = 0.f;
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky) {
+    const int iy = oy + ky - 1;
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int ix = ox + kx - 1;
+      if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
+        const f32x4 v = *(const f32x4*)(mr + (m + (int64_t)(ky - 1) * W + (kx - 1)) * ld);
+        const f32x4 wt = *(const f32x4*)(w2 + (ky * 3 + kx) * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = fmaf(wt[j], v[j], acc);
+      }
+    }
+  }
+  const float s = 1.0f / (1.0f + expf(-acc));
+  e[m] = fmaf(s, mr[m * ld + 4], br);
+}
+
+struct fuse_params {
+  const float* e[4];
+  float wc[4];
+  float bc;
+  int H, W;
+  int64_t npix;
+  float* out;
+};
+
+// F.interpolate(mode="bilinear", align_corners=False) from a map of (H >> s) x (W >> s): source coordinate
+// (dst + 0.5) / 2^s - 0.5 clamped at 0 (exact in fp32: the ratio is a power of two), second tap clamped to the last row /
+// column; s = 0 is the identity.
+__device__ __forceinline__ float bilinear_pow2(const float* __restrict__ e, int h, int w, int s, int oy, int ox) {
+  const float sc = 1.0f / (float)(1 << s);
+  const float fy = fmaxf(((float)oy + 0.5f) * sc - 0.5f, 0.f), fx = fmaxf(((float)ox + 0.5f) * sc - 0.5f, 0.f);
+  const int y0 = (int)fy, x0 = (int)fx;
+  const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
+  const float ly = fy - (float)y0, lx = fx - (float)x0;
+  const float hy = 1.0f - ly, hx = 1.0f - lx;
+  const float v00 = e[(int64_t)y0 * w + x0], v01 = e[(int64_t)y0 * w + x1];
+  const float v10 = e[(int64_t)y1 * w + x0], v11 = e[(int64_t)y1 * w + x1];
+  return hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+}
+
+__global__ __launch_bounds__(256) void pidinet_fuse_kernel(const fuse_params p) {
+  const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (m >= p.npix) return;
+  const int64_t hw = (int64_t)p.H * p.W;
+  const int64_t img = m / hw;
+  const int rem = (int)(m - img * hw);
+  const int oy = rem / p.W, ox = rem - oy * p.W;
+  float acc = p.bc;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int h = p.H >> s, w = p.W >> s;
+    acc = fmaf(p.wc[s], bilinear_pow2(p.e[s] + img * (int64_t)h * w, h, w, s, oy, ox), acc);
+  }
+  p.out[m] = 1.0f / (1.0f + expf(-acc));
+}
+
+}  // namespace
+
+extern "C" int vgen_dwconv_relu(const float* x, int64_t ldx, int64_t n, int32_t H, int32_t W, int32_t Cp, const float* w,
+                                int32_t k, int32_t pool, float* xp, void* xp16, void* y, int32_t dtype, void* stream) {
+  VGEN_REQUIRE(dtype == VGEN_BF16 || dtype == VGEN_F16, "dwconv_relu: dtype must be VGEN_BF16 or VGEN_F16");
+  VGEN_REQUIRE(x && y, "dwconv_relu: x and y must be non-null");
+  VGEN_REQUIRE(k == 1 || k == 3 || k == 5, "dwconv_relu: k = %d must be 1, 3 or 5", (int)k);
+  VGEN_REQUIRE((k == 1) == (w == nullptr), "dwconv_relu: w must be NULL for k = 1 and non-null for k = 3, 5");
+  VGEN_REQUIRE(pool == 0 || pool == 1, "dwconv_relu: pool must be 0 or 1");
+  VGEN_REQUIRE(Cp > 0 && Cp % 64 == 0 && Cp <= 1024, "dwconv_relu: Cp = %d must be a positive multiple of 64, <= 1024", (int)Cp);
+  VGEN_REQUIRE(n >= 0 && H > 0 && W > 0 && n * (int64_t)H * W < (1LL << 31), "dwconv_relu: n >= 0, H, W > 0, n H W < 2^31");
+  VGEN_REQUIRE(ldx >= Cp && ldx % 4 == 0 && ldx < (1LL << 30), "dwconv_relu: ldx = %lld must be >= Cp and a multiple of 4", (long long)ldx);
+  VGEN_REQUIRE(vgen_aligned16(x) && vgen_aligned16(w) && vgen_aligned16(y) && vgen_aligned16(xp) && vgen_aligned16(xp16),
+               "dwconv_relu: every pointer must be 16-byte aligned");
+  if (pool)
+    VGEN_REQUIRE(xp && xp16 && H % 2 == 0 && W % 2 == 0, "dwconv_relu: pool = 1 needs xp, xp16 and even H = %d, W = %d", (int)H, (int)W);
+  else
+    VGEN_REQUIRE(!xp && !xp16, "dwconv_relu: xp and xp16 must be NULL without pool");
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const int C4 = Cp / 4;
+  const float* src = x;
+  int64_t lds = ldx;
+  int h = H, wd = W;
+  if (pool) {
+    h = H / 2;
+    wd = W / 2;
+    const int64_t total = n * h * wd * C4;
+    const int64_t grid = (total + 255) / 256;
+    VGEN_REQUIRE(grid < (1LL << 31), "dwconv_relu: too large");
+    if (dtype == VGEN_BF16)
+      hipLaunchKernelGGL(pool2x2_kernel<BF16>, dim3((unsigned)grid), dim3(256), 0, s, x, ldx, total, H, W, C4, xp, (uint16_t*)xp16);
+    else
+      hipLaunchKernelGGL(pool2x2_kernel<F16>, dim3((unsigned)grid), dim3(256), 0, s, x, ldx, total, H, W, C4, xp, (uint16_t*)xp16);
+    const int rc = vgen_check_launch("dwconv_relu(pool)");
+    if (rc) return rc;
+    src = xp;
+    lds = Cp;
+  }
+  const int64_t total = n * h * ((wd + DW_PX - 1) / DW_PX) * C4;
+  const int64_t grid = (total + 255) / 256;
+  VGEN_REQUIRE(grid < (1LL << 31), "dwconv_relu: too large");
+#define VGEN_DW_LAUNCH(TT, KK) \
+  hipLaunchKernelGGL((dwconv_relu_kernel<TT, KK>), dim3((unsigned)grid), dim3(256), 0, s, src, lds, total, h, wd, C4, w, (uint16_t*)y)
+  if (dtype == VGEN_BF16) {
+    if (k == 1) VGEN_DW_LAUNCH(BF16, 1); else if (k == 3) VGEN_DW_LAUNCH(BF16, 3); else VGEN_DW_LAUNCH(BF16, 5);
+  } else {
+    if (k == 1) VGEN_DW_LAUNCH(F16, 1); else if (k == 3) VGEN_DW_LAUNCH(F16, 3); else VGEN_DW_LAUNCH(F16, 5);
+  }
+#undef VGEN_DW_LAUNCH
+  return vgen_check_launch("dwconv_relu");
+}
+
+extern "C" int vgen_cdcm_head(const void* t, int64_t ldt, int64_t n, int32_t H, int32_t W, const void* Wd, const float* Wa,
+                              const float* ba, const float* wr, float* out, int64_t ldo, int32_t dtype, void* stream) {
+  VGEN_REQUIRE(dtype == VGEN_BF16 || dtype == VGEN_F16, "cdcm_head: dtype must be VGEN_BF16 or VGEN_F16");
+  VGEN_REQUIRE(t && Wd && Wa && ba && wr && out, "cdcm_head: t, Wd, Wa, ba, wr and out must be non-null");
+  VGEN_REQUIRE(n >= 0 && H > 0 && W > 0 && n * (int64_t)H * W < (1LL << 31), "cdcm_head: n >= 0, H, W > 0, n H W < 2^31");
+  VGEN_REQUIRE(ldt >= CD_C && ldt % 8 == 0 && ldt < (1LL << 30), "cdcm_head: ldt = %lld must be >= 32 and a multiple of 8", (long long)ldt);
+  VGEN_REQUIRE(ldo >= 5 && ldo % 4 == 0 && ldo < (1LL << 30), "cdcm_head: ldo = %lld must be >= 5 and a multiple of 4", (long long)ldo);
+  VGEN_REQUIRE(vgen_aligned16(t) && vgen_aligned16(Wd) && vgen_aligned16(Wa) && vgen_aligned16(ba) && vgen_aligned16(wr) &&
+                   vgen_aligned16(out),
+               "cdcm_head: every pointer must be 16-byte aligned");
+  if (n == 0) return 0;
+  cdcm_params p;
+  p.t = (const uint16_t*)t; p.ldt = ldt; p.H = H; p.W = W;
+  p.tiles_x = (W + CD_TW - 1) / CD_TW; p.tiles_y = (H + CD_TH - 1) / CD_TH;
+  p.Wd = (const uint16_t*)Wd; p.Wa = Wa; p.ba = ba; p.wr = wr; p.out = out; p.ldo = ldo;
+  const int64_t grid = n * p.tiles_x * p.tiles_y;
+  VGEN_REQUIRE(grid < (1LL << 31), "cdcm_head: too large");
+  static bool attr_done[VGEN_MAX_DEVICES] = {false};   // the LDS opt-in is per device
+  const int dev = vgen_device_slot();
+  if (!attr_done[dev]) {
+    hipError_t e1 = hipFuncSetAttribute((const void*)cdcm_head_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_LDS);
+    hipError_t e2 = hipFuncSetAttribute((const void*)cdcm_head_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_LDS);
+    if (e1 != hipSuccess || e2 != hipSuccess) {
+      vgen_set_error("cdcm_head: hipFuncSetAttribute(%d B LDS) failed", CD_LDS);
+      return (int)(e1 != hipSuccess ? e1 : e2);
+    }
+    attr_done[dev] = true;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == VGEN_BF16)
+    hipLaunchKernelGGL(cdcm_head_kernel<BF16>, dim3((unsigned)grid), dim3(256), CD_LDS, s, p);
+  else
+    hipLaunchKernelGGL(cdcm_head_kernel<F16>, dim3((unsigned)grid), dim3(256), CD_LDS, s, p);
+  return vgen_check_launch("cdcm_head");
+}
+
+extern "C" int vgen_pidinet_emap(const float* mr, int64_t ld, int64_t n, int32_t H, int32_t W, const float* w2, float br,
+                                 float* e, void* stream) {
+  VGEN_REQUIRE(mr && w2 && e, "pidinet_emap: mr, w2 and e must be non-null");
+  VGEN_REQUIRE(n >= 0 && H > 0 && W > 0 && n * (int64_t)H * W < (1LL << 31), "pidinet_emap: n >= 0, H, W > 0, n H W < 2^31");
+  VGEN_REQUIRE(ld >= 5 && ld % 4 == 0 && ld < (1LL << 30), "pidinet_emap: ld = %lld must be >= 5 and a multiple of 4", (long long)ld);
+  VGEN_REQUIRE(br == br, "pidinet_emap: br must not be NaN");
+  VGEN_REQUIRE(vgen_aligned16(mr) && vgen_aligned16(w2) && (((uintptr_t)e) & 3u) == 0,
+               "pidinet_emap: mr / w2 must be 16-byte, e 4-byte aligned");
+  if (n == 0) return 0;
+  const int64_t npix = n * (int64_t)H * W;
+  hipLaunchKernelGGL(pidinet_emap_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, mr, ld, npix,
+                     H, W, w2, br, e);
+  return vgen_check_launch("pidinet_emap");
+}
+
+extern "C" int vgen_pidinet_fuse(const float* e0, const float* e1, const float* e2, const float* e3, int64_t n, int32_t H,
+                                 int32_t W, float wc0, float wc1, float wc2, float wc3, float bc, float* out, void* stream) {
+  VGEN_REQUIRE(e0 && e1 && e2 && e3 && out, "pidinet_fuse: e0..e3 and out must be non-null");
+  VGEN_REQUIRE(n >= 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "pidinet_fuse: H = %d and W = %d must be positive multiples of 8",
+               (int)H, (int)W);
+  VGEN_REQUIRE(n * (int64_t)H * W < (1LL << 31), "pidinet_fuse: n H W must be < 2^31");
+  VGEN_REQUIRE(wc0 == wc0 && wc1 == wc1 && wc2 == wc2 && wc3 == wc3 && bc == bc, "pidinet_fuse: classifier weights must not be NaN");
+  VGEN_REQUIRE(((((uintptr_t)e0) | ((uintptr_t)e1) | ((uintptr_t)e2) | ((uintptr_t)e3) | ((uintptr_t)out)) & 3u) == 0,
+               "pidinet_fuse: every pointer must be 4-byte aligned");
+  if (n == 0) return 0;
+  fuse_params p;
+  p.e[0] = e0; p.e[1] = e1; p.e[2] = e2; p.e[3] = e3;
+  p.wc[0] = wc0; p.wc[1] = wc1; p.wc[2] = wc2; p.wc[3] = wc3;
+  p.bc = bc; p.H = H; p.W = W; p.npix = n * (int64_t)H * W; p.out = out;
+  hipLaunchKernelGGL(pidinet_fuse_kernel, dim3((unsigned)((p.npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+  return vgen_check_launch("pidinet_fuse");
+}

@@ -409,6 +409,105 @@ class HipBackend:
         _lib.check(rc, "vgen_adapter")
         return out
 
+    # -- sketch annotator (include/vgen_hip.h: "Sketch annotator") ----------------------------------------------
+    def sketch_stem(self, x, flip, mean, std, w, b, dt):
+        """frames [n, 1, H, W] fp32 -> 16-bit rows [n * H/2 * W/2, 64] = relu(conv5x5/s2(((1 - x | x) - mean) / std) + b)."""
+        assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 1
+        assert w.dtype == torch.float32 and w.is_contiguous() and w.shape == (25, 64)
+        assert b.dtype == torch.float32 and b.is_contiguous() and b.shape == (64,)
+        n, _, H, W = x.shape
+        out = torch.empty((n * (H // 2) * (W // 2), 64), dtype=dt, device=x.device)
+        with self._Prof("sketch_stem", 4.0 * x.numel() + 2.0 * out.numel(), (n, H, W)):
+            rc = self.lib.vgen_sketch_stem(_ptr(x), n, H, W, int(bool(flip)), float(mean), float(std), _ptr(w), _ptr(b),
+                                           _ptr(out), out.stride(0), _ENUM[dt], self._stream(x))
+        _lib.check(rc, "vgen_sketch_stem")
+        return out
+
+    def relu_shuffle16(self, a, C, g=1, Hin=0, Win=0, out=None):
+        """16-bit rows [M, g*g*C] -> relu -> rows [(img, g y + py, g x + px), C]; g = 1 defaults to in place."""
+        a = _mat(a, "a")
+        M = a.shape[0]
+        assert a.dtype in (torch.float16, torch.bfloat16) and a.shape[1] >= g * g * C
+        if out is None:
+            out = a if g == 1 else torch.empty((M * g * g, C), dtype=a.dtype, device=a.device)
+        _mat(out, "out")
+        assert out.dtype == a.dtype and out.shape[0] == M * g * g and out.shape[1] >= C
+        with self._Prof("relu_shuffle16", 4.0 * M * g * g * C, (M, C, g)):
+            rc = self.lib.vgen_relu_shuffle16(_ptr(a), a.stride(0), M, int(C), int(g), int(Hin), int(Win), _ptr(out),
+                                              out.stride(0), _ENUM[a.dtype], self._stream(a))
+        _lib.check(rc, "vgen_relu_shuffle16")
+        return out
+
+    def sketch_head(self, a, n, H, W, C, w, bias, flip):
+        """16-bit rows [n H W, >= C] -> fp32 [n, 1, H, W] = sigmoid(conv3x3(a) + bias), or 1 - that (flip)."""
+        a = _mat(a, "a")
+        assert a.dtype in (torch.float16, torch.bfloat16) and a.shape[0] == n * H * W and a.shape[1] >= C
+        assert w.dtype == torch.float32 and w.is_contiguous() and w.shape == (9, C)
+        out = torch.empty((n, 1, H, W), dtype=torch.float32, device=a.device)
+        with self._Prof("sketch_head", 2.0 * a.shape[0] * C * 9 + 4.0 * out.numel(), (n, H, W, C)):
+            rc = self.lib.vgen_sketch_head(_ptr(a), a.stride(0), n, H, W, int(C), _ptr(w), float(bias), int(bool(flip)),
+                                           _ptr(out), _ENUM[a.dtype], self._stream(a))
+        _lib.check(rc, "vgen_sketch_head")
+        return out
+
+    def dwconv_relu(self, x, n, H, W, w, k, dt, pool=False):
+        """fp32 rows [n H W, Cp] -> 16-bit rows relu(depthwise k x k conv) (vgen_dwconv_relu); w fp32 [k*k, Cp], None for
+        k = 1 (the plain ReLU-cast).  pool: 2x2 max-pool first -> (pooled fp32 rows, their 16-bit cast, conv rows), all
+        [n H/2 W/2, Cp]."""
+        x = _mat(x, "x")
+        Cp = x.shape[1]
+        assert x.dtype == torch.float32 and x.shape[0] == n * H * W
+        assert (w is None) == (k == 1) and (w is None or (w.dtype == torch.float32 and w.is_contiguous() and w.shape == (k * k, Cp)))
+        M = n * (H // 2) * (W // 2) if pool else n * H * W
+        y = torch.empty((M, Cp), dtype=dt, device=x.device)
+        xp = torch.empty((M, Cp), dtype=torch.float32, device=x.device) if pool else None
+        xp16 = torch.empty((M, Cp), dtype=dt, device=x.device) if pool else None
+        nbytes = 4.0 * x.numel() + 2.0 * y.numel() + (10.0 * M * Cp if pool else 0.0)
+        with self._Prof("dwconv_relu", nbytes, (n, H, W, Cp, k, int(bool(pool)))):
+            rc = self.lib.vgen_dwconv_relu(_ptr(x), x.stride(0), n, H, W, Cp, _ptr(w), int(k), int(bool(pool)), _ptr(xp),
+                                           _ptr(xp16), _ptr(y), _ENUM[dt], self._stream(x))
+        _lib.check(rc, "vgen_dwconv_relu")
+        return (xp, xp16, y) if pool else y
+
+    def cdcm_head(self, t, n, H, W, Wd, Wa, ba, wr, out=None):
+        """16-bit rows t [n H W, >= 32] -> fp32 rows [n H W, 8]: columns 0..3 = Wa . relu(u) + ba, 4 = wr . u, u = the sum
+        of the four dilated 3x3 convs of t (vgen_cdcm_head); columns 5..7 are not written."""
+        t = _mat(t, "t")
+        assert t.dtype in (torch.float16, torch.bfloat16) and t.shape[0] == n * H * W and t.shape[1] >= 32
+        assert Wd.dtype == t.dtype and Wd.is_contiguous() and Wd.shape == (4, 9, 32, 32)
+        assert Wa.dtype == torch.float32 and Wa.is_contiguous() and Wa.shape == (4, 32)
+        assert ba.dtype == torch.float32 and ba.shape == (4,) and wr.dtype == torch.float32 and wr.shape == (32,)
+        if out is None:
+            out = torch.empty((n * H * W, 8), dtype=torch.float32, device=t.device)
+        _mat(out, "out")
+        assert out.dtype == torch.float32 and out.shape[0] == n * H * W and out.shape[1] >= 5
+        with self._Prof("cdcm_head", 2.0 * n * H * W * 36 * 32 * 32, (n, H, W)):
+            rc = self.lib.vgen_cdcm_head(_ptr(t), t.stride(0), n, H, W, _ptr(Wd), _ptr(Wa), _ptr(ba), _ptr(wr), _ptr(out),
+                                         out.stride(0), _ENUM[t.dtype], self._stream(t))
+        _lib.check(rc, "vgen_cdcm_head")
+        return out
+
+    def pidinet_emap(self, mr, n, H, W, w2, br):
+        """rows (m0..m3, r) [n H W, >= 5] fp32 -> edge map [n, H, W] fp32 = sigmoid(conv3x3(m)) * r + br."""
+        mr = _mat(mr, "mr")
+        assert mr.dtype == torch.float32 and mr.shape[0] == n * H * W and mr.shape[1] >= 5
+        assert w2.dtype == torch.float32 and w2.is_contiguous() and w2.shape == (9, 4)
+        e = torch.empty((n, H, W), dtype=torch.float32, device=mr.device)
+        rc = self.lib.vgen_pidinet_emap(_ptr(mr), mr.stride(0), n, H, W, _ptr(w2), float(br), _ptr(e), self._stream(mr))
+        _lib.check(rc, "vgen_pidinet_emap")
+        return e
+
+    def pidinet_fuse(self, es, n, H, W, wc, bc):
+        """four edge maps [n, H >> i, W >> i] fp32 -> [n, 1, H, W] fp32 = sigmoid(bc + sum_i wc[i] bilinear(e_i))."""
+        assert len(es) == 4 and len(wc) == 4
+        for i, e in enumerate(es):
+            assert e.dtype == torch.float32 and e.is_contiguous() and tuple(e.shape) == (n, H >> i, W >> i), (i, tuple(e.shape))
+        out = torch.empty((n, 1, H, W), dtype=torch.float32, device=es[0].device)
+        rc = self.lib.vgen_pidinet_fuse(_ptr(es[0]), _ptr(es[1]), _ptr(es[2]), _ptr(es[3]), n, H, W, float(wc[0]),
+                                        float(wc[1]), float(wc[2]), float(wc[3]), float(bc), _ptr(out), self._stream(es[0]))
+        _lib.check(rc, "vgen_pidinet_fuse")
+        return out
+
     # -- condition stems (fp32, NCHW frames; once per sampling session) ------------------------------------
     def conv3x3_small(self, x, w, b, stride=1, act=0):
         assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
