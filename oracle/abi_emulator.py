@@ -21,6 +21,9 @@ def _strided(t, sizes, strides):
     return torch.as_strided(t, sizes, strides, t.storage_offset())
 
 
+GN_CS_GUARD = 128.0   # csrc/norms.hip: the statistics path re-centres where N mean^2 > GN_CS_GUARD * M2
+
+
 class EmuBackend:
     name = "emu"
 
@@ -41,6 +44,13 @@ class EmuBackend:
             n = S * (C // groups)
             mean64 = t[:, 0] / n
             var64 = (t[:, 1] / n - mean64 * mean64).clamp_min(0)
+            # gn_finalize_cs_kernel's conditioning guard (csrc/norms.hip GN_CS_GUARD): where N M^2 > 128 Q the fp32 column
+            # sums cannot carry the variance, and the kernel takes it from x itself, centred about the mean
+            guard = mean64 * mean64 > GN_CS_GUARD * var64
+            if bool(guard.any()):
+                v64 = v.double()
+                mean64 = torch.where(guard, v64.mean(dim=(1, 3)), mean64)
+                var64 = torch.where(guard, v64.var(dim=(1, 3), unbiased=False), var64)
             mean = mean64.float().view(nb, 1, groups, 1)
             var = var64.float().view(nb, 1, groups, 1)
         else:

@@ -58,10 +58,17 @@ __device__ __forceinline__ f32x4 gn_load(const float* x1, const float* x2, const
 // ws layout: part[nb][nsplit][groups][3] (count, mean, M2) then stat[nb][C][2]: per-channel
 // (scale, shift) = (gamma * rstd, beta - mean * gamma * rstd), written by the finalize kernels so that the
 // apply blocks start streaming after two coalesced loads instead of 16 dependent scalar ones
+//
+// Shifted moments.  Raw sum x^2 - (sum x)^2 / n loses (mean / sigma)^2 of relative accuracy in fp32 (rstd off by 1.5 % at
+// mean / sigma = 1000).  Every thread therefore accumulates sum (x - p) and sum (x - p)^2 per channel about a pivot p of its
+// own, the first row it loads (no extra load, no broadcast), and leaves (mean, M2) of its chain of <= 51 rows: the loss is
+// ((chain mean - p) / chain sigma)^2 = O(1), and a pivot that happens to be an outlier spoils only the chain that holds the
+// outlier anyway.  One thread per group then merges the rpb * cpg chains of the group in a fixed order: mean about the first
+// chain's mean, M2 = sum M2_i + sum n_i (mean_i - mean)^2.
 __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(
     const float* __restrict__ x1, int C1, const float* __restrict__ x2, int C2, int64_t S,
     int groups, int nsplit, float* __restrict__ part) {
-  __shared__ float red[2][3072];  // [sum|sumsq][rowlane * C + c]  (rpb * C <= 1024 when rpb > 1)
+  __shared__ float red[2][3072];  // [mean|M2][rowlane * C + c]  (rpb * C <= 1024 when rpb > 1)
   const GnGeom g = gn_geom(C1, C2, groups);
   const int tid = threadIdx.x;
   const int split = blockIdx.x;
@@ -69,17 +76,21 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(
   const int64_t rows_per = (S + nsplit - 1) / nsplit;
   const int64_t r_begin = (int64_t)split * rows_per;
   const int64_t r_end = min(S, r_begin + rows_per);
+  const int nrows = r_end > r_begin ? (int)(r_end - r_begin) : 0;
   const int rowlane = tid / g.tpr;
   const int slot0 = tid - rowlane * g.tpr;
-  const bool active = rowlane < g.rpb;
 
-  f32x4 s[GN_MAX_SLOTS], ss[GN_MAX_SLOTS];
+  if (rowlane < g.rpb) {
+    const int cnt = nrows > rowlane ? (nrows - rowlane + g.rpb - 1) / g.rpb : 0;   // rows of this thread's chain
+    f32x4 s[GN_MAX_SLOTS], ss[GN_MAX_SLOTS], pv[GN_MAX_SLOTS];
 #pragma unroll
-  for (int k = 0; k < GN_MAX_SLOTS; ++k) {
-    s[k] = f32x4{0, 0, 0, 0};
-    ss[k] = f32x4{0, 0, 0, 0};
-  }
-  if (active) {
+    for (int k = 0; k < GN_MAX_SLOTS; ++k) {
+      s[k] = f32x4{0, 0, 0, 0};
+      ss[k] = f32x4{0, 0, 0, 0};
+      pv[k] = f32x4{0, 0, 0, 0};
+    }
+    // the pivot is taken inside the loop (first trip) so that the loads of the first rows stay in flight together
+    bool first = true;
 #pragma unroll 4
     for (int64_t r = r_begin + rowlane; r < r_end; r += g.rpb) {
       const int64_t row = nb * S + r;
@@ -87,35 +98,57 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(
       for (int k = 0; k < GN_MAX_SLOTS; ++k) {
         const int slot = slot0 + k * GN_THREADS;
         if (k < g.spt && slot < g.nslots) {
-          const f32x4 v = gn_load(x1, x2, g, row, slot * 4);
+          const f32x4 x = gn_load(x1, x2, g, row, slot * 4);
+          if (first) pv[k] = x;
+          const f32x4 v = x - pv[k];
           s[k] += v;
           ss[k] += v * v;
         }
       }
+      first = false;
     }
+    const float inv = cnt > 0 ? 1.0f / (float)cnt : 0.f;
 #pragma unroll
     for (int k = 0; k < GN_MAX_SLOTS; ++k) {
       const int slot = slot0 + k * GN_THREADS;
       if (k < g.spt && slot < g.nslots) {
         const int o = rowlane * g.C + slot * 4;
-        *(f32x4*)&red[0][o] = s[k];
-        *(f32x4*)&red[1][o] = ss[k];
+        const f32x4 dm = s[k] * inv;
+        f32x4 m2 = ss[k] - s[k] * dm;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m2[e] = fmaxf(m2[e], 0.f);
+        *(f32x4*)&red[0][o] = pv[k] + dm;
+        *(f32x4*)&red[1][o] = m2;
       }
     }
   }
   __syncthreads();
   if (tid < groups) {
-    float a = 0.f, b = 0.f;
-    for (int rl = 0; rl < g.rpb; ++rl) {
-      const int o = rl * g.C + tid * g.cpg;
-      for (int c = 0; c < g.cpg; ++c) {
-        a += red[0][o + c];
-        b += red[1][o + c];
+    const float n = (float)nrows * (float)g.cpg;
+    float mean = 0.f, m2 = 0.f;
+    if (nrows > 0) {
+      const float ref = red[0][tid * g.cpg];     // row lane 0 always holds a row of a non-empty slab
+      float a = 0.f;
+      for (int rl = 0; rl < g.rpb; ++rl) {
+        const float cnt = nrows > rl ? (float)((nrows - rl + g.rpb - 1) / g.rpb) : 0.f;
+        const int o = rl * g.C + tid * g.cpg;
+        float t = 0.f;
+        for (int c = 0; c < g.cpg; ++c) t += red[0][o + c] - ref;
+        a += cnt * t;                            // an empty chain staged zeros and counts 0
+      }
+      mean = ref + a / n;
+      for (int rl = 0; rl < g.rpb; ++rl) {
+        const float cnt = nrows > rl ? (float)((nrows - rl + g.rpb - 1) / g.rpb) : 0.f;
+        const int o = rl * g.C + tid * g.cpg;
+        float t = 0.f, q = 0.f;
+        for (int c = 0; c < g.cpg; ++c) {
+          const float d = red[0][o + c] - mean;
+          t += d * d;
+          q += red[1][o + c];
+        }
+        m2 += q + cnt * t;
       }
     }
-    const float n = (float)((r_end > r_begin ? (r_end - r_begin) : 0) * g.cpg);
-    const float mean = n > 0.f ? a / n : 0.f;
-    const float m2 = n > 0.f ? fmaxf(b - a * mean, 0.f) : 0.f;
     float* o = part + ((nb * nsplit + split) * groups + tid) * 3;
     o[0] = n;
     o[1] = mean;
@@ -189,18 +222,29 @@ __device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2, flo
   n = nt;
 }
 
+// Conditioning guard.  A slab's M2 = sq - sm^2 / 64 comes from sums the producer's epilogue formed in fp32 (4 sequential
+// terms per lane, then a 16-term pairwise fold: <= 7 roundings each, one more for a square): |error of sq| <= 8 * 2^-24 * sq,
+// |error of sm^2 / 64| <= 16 * 2^-24 * sm^2 / 64, together <= 24 * 2^-24 * 64 (mean^2 + var) per item, so the merged variance
+// Q / N is off by <= 24 * 2^-24 * (N M^2 / Q + 1) relative.  rstd within u_fp16 / 4 = 2^-13 needs the variance within
+// 2^-12: N M^2 / Q <= 2^12 / 24 - 1 = 169; the guard takes the power of two below.  Beyond it the block streams its own slice of
+// x once and takes the variance centred about the merged mean M (itself good to 7 * 2^-24 relative), with the
+// first-moment correction.  Activations of the UNet sit at N M^2 / Q < 1: the guard costs them one compare and leaves their
+// results as they were, bit for bit.
+constexpr float GN_CS_GUARD = 128.f;
+
 // r04: NT = 1024 for the 5-D norms of the big levels (448 slabs x 10..40 channels = 4.5 K - 18 K items per group: 18 - 70
 // dependent L2 round trips per thread at 256 threads were most of this launch's ~10 us; 68 such launches per step).
 template <int NT>
 __global__ __launch_bounds__(NT) void gn_finalize_cs_kernel(const float* __restrict__ cs1, int C1,
                                                              const float* __restrict__ cs2, int C2,
+                                                             const float* __restrict__ x1, const float* __restrict__ x2,
                                                              int64_t S, int groups, float eps,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta,
                                                              float* __restrict__ stat) {
   constexpr int NW = NT / 64;
   __shared__ float red[NW][3];
-  __shared__ float mr[2];
+  __shared__ float mr[3];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int grp = blockIdx.x;
   const int64_t nb = blockIdx.y;
@@ -266,8 +310,45 @@ __global__ __launch_bounds__(NT) void gn_finalize_cs_kernel(const float* __restr
     const float var = N > 0.f ? Q / N : 0.f;
     mr[0] = M;
     mr[1] = 1.0f / sqrtf(var + eps);
+    mr[2] = N * M * M > GN_CS_GUARD * Q ? 1.f : 0.f;
   }
   __syncthreads();
+  if (mr[2] != 0.f) {   // block-uniform: ill-conditioned raw moments, centred second pass over this (batch, group) slice
+    const float M = mr[0];
+    const int64_t tot = S * cpg;
+    float d = 0.f, q = 0.f;
+    for (int64_t i = tid; i < tot; i += NT) {
+      const int64_t r = i / cpg;
+      const int c = grp * cpg + (int)(i - r * cpg);
+      const int64_t row = nb * S + r;
+      const float e = (c < C1 ? x1[row * C1 + c] : x2[row * C2 + (c - C1)]) - M;
+      d += e;
+      q += e * e;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      d += __shfl_xor(d, o, 64);
+      q += __shfl_xor(q, o, 64);
+    }
+    __syncthreads();     // every thread has read mr[0]; thread 0 is done with red[]
+    if (lane == 0) {
+      red[w][0] = d;
+      red[w][1] = q;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      float D = red[0][0], Q = red[0][1];
+      for (int k = 1; k < NW; ++k) {
+        D += red[k][0];
+        Q += red[k][1];
+      }
+      const float nf = (float)tot;
+      const float dm = D / nf;
+      mr[0] = M + dm;
+      mr[1] = 1.0f / sqrtf(fmaxf(Q - D * dm, 0.f) / nf + eps);
+    }
+    __syncthreads();
+  }
   const int C = C1 + C2;
   for (int j = tid; j < cpg; j += NT) {
     const int c = grp * cpg + j;
@@ -823,10 +904,10 @@ static int groupnorm_impl(const float* x1, int32_t C1, const float* cs1, const f
   if (cs1 != nullptr) {
     if ((S / 64) * (C / groups) > 2048) {
       hipLaunchKernelGGL(gn_finalize_cs_kernel<1024>, dim3((unsigned)groups, (unsigned)nb), dim3(1024), 0, s, cs1, C1,
-                         cs2, C2, S, groups, eps, gamma, beta, stat);
+                         cs2, C2, x1, x2, S, groups, eps, gamma, beta, stat);
     } else {
       hipLaunchKernelGGL(gn_finalize_cs_kernel<256>, dim3((unsigned)groups, (unsigned)nb), dim3(256), 0, s, cs1, C1,
-                         cs2, C2, S, groups, eps, gamma, beta, stat);
+                         cs2, C2, x1, x2, S, groups, eps, gamma, beta, stat);
     }
     rc = vgen_check_launch("gn_finalize_cs");
     if (rc) return rc;
