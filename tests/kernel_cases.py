@@ -419,7 +419,7 @@ def r06_shape_cases(dt):
 
 
 def plan_signature(g):
-    """The 9 integers a plan-table row is keyed on (csrc/tapgemm.hip PlanEntry)."""
+    """The 9 integers a plan-table row is keyed on (csrc/tapgemm_plan.cpp PlanEntry)."""
     from vgen_amd.ops import _ENUM
     flags = (1 if g.residual is not None else 0) | (2 if g.rowbias is not None else 0) | (4 if g.colstats else 0)
     return (g.mode, g.M, g.N, g.C1, g.C2, g.taps, g.epilogue, _ENUM[g.out_dtype], flags)

@@ -87,12 +87,7 @@ def test_hot_kernels_have_no_register_spills(tmp_path):
     import subprocess
     from vgen_amd import build as b
     for src in ("tapgemm.hip", "panelgemm.hip", "attention.hip"):
-        out = tmp_path / (src + ".s")
-        r = subprocess.run([b._hipcc()] + [f for f in b.FLAGS if f not in ("-fPIC",)] +
-                           ["-S", "--cuda-device-only", os.path.join(b.CSRC, src), "-o", str(out)],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        txt = out.read_text()
+        txt = b.device_asm(src, str(tmp_path / (src + ".s")))
         names = re.findall(r"\.name:\s+(\S+)", txt)
         spills = [int(v) for v in re.findall(r"\.vgpr_spill_count:\s+(\d+)", txt)]
         assert len(spills) >= 6 and all(s == 0 for s in spills), list(zip(names, spills))
@@ -100,21 +95,14 @@ def test_hot_kernels_have_no_register_spills(tmp_path):
             # "product kernels instruction-identical" must be something a test enforces.  The instruction
             # stream of the product build is pinned to a committed fingerprint: whoever edits the kernel refreshes it with
             # `python tools/check_isa.py --update-hash` — and reruns the GPU parity cases on that build in the same change.
-            import hashlib
-            keep = []
-            for l in txt.split("\n"):
-                l = l.split(";")[0].strip()
-                if not l or l.startswith(".") or l.endswith(":") or l.startswith("__hip_cuid"):
-                    continue
-                keep.append(" ".join(l.split()))
-            fp = hashlib.sha256("\n".join(keep).encode()).hexdigest()
-            want_lines = open(os.path.join(os.path.dirname(__file__), "golden", "tapgemm_isa.sha256")).read().split("\n")
-            want = want_lines[0].strip()
+            # The fingerprint is per kernel (vgen_amd/build.py::isa_fingerprint): any changed, added or removed instruction
+            # of any instantiation moves it, the order in which the compiler emits the instantiations does not.
+            fp, table = b.isa_fingerprint(txt)
+            want, pinned_cc, pinned = b.read_isa_pin(os.path.join(os.path.dirname(__file__), "golden", "tapgemm_isa.sha256"))
             # the fingerprint belongs to ONE compiler: under another hipcc the same source legitimately compiles to another
             # stream, and a refreshed hash without a GPU parity run is exactly what this test is there to prevent
-            pinned_cc = next((l.split(":", 1)[1].strip() for l in want_lines[1:] if l.startswith("hipcc:")), None)
             here_cc = subprocess.run([b._hipcc(), "--version"], capture_output=True, text=True).stdout.split("\n")[0].strip()
             if pinned_cc and pinned_cc != here_cc:
                 pytest.skip(f"tap-GEMM ISA fingerprint was taken with '{pinned_cc}', this is '{here_cc}'")
             assert fp == want, ("tap-GEMM product ISA changed: refresh tests/golden/tapgemm_isa.sha256 (tools/check_isa.py "
-                                "--update-hash) and rerun the GPU kernel parity cases", fp)
+                                "--update-hash) and rerun the GPU kernel parity cases", fp, b.isa_moved(table, pinned))

@@ -1,4 +1,4 @@
-"""CPU-side ISA audit of tapgemm.hip (hipcc cross-compiles gfx950 without a GPU):  python tools/check_isa.py [-DVGEN_X ...]
+"""CPU-side ISA audit of tapgemm.hip (hipcc cross-compiles gfx950 without a GPU):  python tools/check_isa.py [-DVGEN_X ...] [--per-kernel]
 
 For the build with the given defines: register spills per kernel, waterfall loops (a `buffer_load` whose resource /
 scalar offset instruction selection found in a VGPR: v_readfirstlane + s_cbranch_execnz around it) and, for the
@@ -7,7 +7,7 @@ probe says costs time).  With --uniformity also: LLVM's own uniformi
 instantiation (`opt -passes='print<uniformity>'`) — private-memory allocas that survived (a load from one is divergent
 by definition: r03 found two local arrays tail-merged into a pointer phi that way) and every LDS-DMA call whose resource
 or scalar offset the analysis calls divergent (each becomes a waterfall loop)."""
-import hashlib, os, re, subprocess, sys
+import os, re, subprocess, sys
 from collections import Counter
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,32 +16,22 @@ from vgen_amd import build as b
 defs = [a for a in sys.argv[1:] if a.startswith("-D")]
 out = os.path.join("/tmp", "tapgemm_" + ("_".join(d[2:] for d in defs) or "product") + ".s")
 flags = [f for f in b.FLAGS if f != "-fPIC"] + defs
-r = subprocess.run([b._hipcc()] + flags + ["-S", "--cuda-device-only", os.path.join(b.CSRC, "tapgemm.hip"), "-o", out],
-                   capture_output=True, text=True)
-assert r.returncode == 0, r.stderr[-3000:]
-t = open(out).read()
+t = b.device_asm("tapgemm.hip", out, defs)
 
-
-def isa_fingerprint(asm_text):
-    """sha256 over the instruction stream of every kernel (labels, directives, comments and the per-compilation
-    __hip_cuid symbol dropped): two sources with the same fingerprint ARE the same machine code.  The product value is
-    committed in tests/golden/tapgemm_isa.sha256 and checked by tests/test_abi.py — a kernel edit has to refresh it
-    (`python tools/check_isa.py --update-hash`) and, with it, rerun the GPU parity cases."""
-    keep = []
-    for l in asm_text.split("\n"):
-        l = l.split(";")[0].strip()
-        if not l or l.startswith(".") or l.endswith(":") or l.startswith("__hip_cuid"):
-            continue
-        keep.append(" ".join(l.split()))
-    return hashlib.sha256("\n".join(keep).encode()).hexdigest(), len(keep)
-
-
-fp, nins = isa_fingerprint(t)
+# the per-kernel fingerprint: vgen_amd/build.py::isa_fingerprint (tests/test_abi.py checks the product value)
+fp, table = b.isa_fingerprint(t)
 HASH_FILE = os.path.join(ROOT, "tests", "golden", "tapgemm_isa.sha256")
-print(f"ISA fingerprint: {fp} ({nins} instructions)")
+print(f"ISA fingerprint: {fp} ({len(table)} kernels, {sum(n for _, n in table.values())} instructions)")
+if "--per-kernel" in sys.argv:
+    for k in sorted(table):
+        print(f"  {table[k][0]} {table[k][1]:6d} {k}")
+if not defs and os.path.exists(HASH_FILE):
+    moved = b.isa_moved(table, b.read_isa_pin(HASH_FILE)[2])
+    print("against the committed fingerprint:", "identical" if not moved else "MOVED: " + ", ".join(moved))
 if "--update-hash" in sys.argv and not defs:
     cc = subprocess.run([b._hipcc(), "--version"], capture_output=True, text=True).stdout.split("\n")[0].strip()
-    open(HASH_FILE, "w").write(fp + "\nhipcc: " + cc + "\n")     # the compiler the stream belongs to (tests/test_abi.py)
+    with open(HASH_FILE, "w") as f:      # digest | the compiler the streams belong to | one `sha256  kernel` line per kernel
+        f.write(fp + "\nhipcc: " + cc + "\n" + "".join(f"{table[k][0]}  {k}\n" for k in sorted(table)))
     print("written to", HASH_FILE)
 vs = [int(x) for x in re.findall(r"\.vgpr_spill_count:\s+(\d+)", t)]
 ss = [int(x) for x in re.findall(r"\.sgpr_spill_count:\s+(\d+)", t)]

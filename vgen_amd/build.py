@@ -6,7 +6,9 @@ travels with the repo snapshot (it is git-ignored, not gpurun-ignored).
 """
 from __future__ import annotations
 
+import hashlib
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -16,10 +18,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libvgen_hip.so")
-SOURCES = ["cabi.cpp", "tapgemm.hip", "panelgemm.hip", "norms.hip", "attention.hip", "misc.hip", "stems.hip", "adapter.hip",
-           "sketch.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "tapgemm_plans.inc"),
-           os.path.join(HERE, "..", "include", "vgen_hip.h")]
+SOURCES = ["cabi.cpp", "tapgemm_plan.cpp", "tapgemm.hip", "panelgemm.hip", "norms.hip", "attention.hip", "misc.hip", "stems.hip",
+           "adapter.hip", "sketch.hip"]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(HERE, "..", "include", "vgen_hip.h")]     # every source's
+# what a source includes beyond HEADERS.  tapgemm_plan.cpp is the tap-GEMM planner: plain C++ (HOST_ONLY: compiled without
+# the HIP language mode, no device pass), so a new plan table (tools/autotune_gemm.py --emit) rebuilds it alone, in seconds
+DEPS = {"tapgemm_plan.cpp": ["tapgemm_plan.h", "tapgemm_plans.inc"], "tapgemm.hip": ["tapgemm_plan.h"],
+        "panelgemm.hip": ["tapgemm_plan.h"]}
+HOST_ONLY = {"tapgemm_plan.cpp"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-inline-asm",
          "-x", "hip"]
 
@@ -100,8 +106,10 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False, vari
         s = os.path.join(CSRC, src)
         o = os.path.join(obj_dir, os.path.splitext(src)[0] + ".o")
         objs.append(o)
-        if force or _stale(o, [s] + HEADERS):
-            jobs.append([hipcc] + flags + ["-c", s, "-o", o])
+        if force or _stale(o, [s] + HEADERS + [os.path.join(CSRC, d) for d in DEPS.get(src, ())]):
+            fl = [f for f in flags if f not in ("-x", "hip") and not f.startswith("--offload-arch")] + ["-x", "c++"] \
+                if src in HOST_ONLY else flags
+            jobs.append([hipcc] + fl + ["-c", s, "-o", o])
 
     def run(cmd):
         if verbose:
@@ -117,6 +125,67 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False, vari
     if force or jobs or _stale(lib_path, objs):
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path] + objs)
     return lib_path
+
+
+def device_asm(src: str, out: str, defines=()) -> str:
+    """gfx950 assembly text of the device code of csrc/<src> (written to `out`), compiled with the library's flags."""
+    cmd = [_hipcc()] + [f for f in FLAGS if f != "-fPIC"] + list(defines) + ["-S", "--cuda-device-only",
+                                                                            os.path.join(CSRC, src), "-o", out]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("build failed: %s\n%s" % (" ".join(cmd), r.stderr[-3000:]))
+    with open(out) as f:
+        return f.read()
+
+
+def isa_fingerprint(asm_text: str):
+    """The machine code of every kernel in a device assembly listing -> (digest, {kernel: (sha256, instructions)}).
+
+    Per kernel: sha256 over its instruction stream (labels, directives and comments dropped, whitespace normalised), with
+    the function index taken out of the local labels an instruction names (`.LBB12_7` -> `.LBB_7`: the index counts the
+    functions the compiler emitted before this one), followed by the kernel's entry of the code-object metadata (argument
+    layout, register counts, LDS and scratch sizes).  What belongs to no kernel (target, metadata version) is hashed as
+    "<module>".  The digest is the sha256 over the (kernel name, stream hash) pairs sorted by name.  It moves with any
+    changed, added or removed instruction of any kernel and with a renamed, missing or extra kernel; it does not move when
+    the compiler emits the same kernels in another order, which is all a host-side edit of a translation unit can do to its
+    device code.  The product value of tapgemm.hip is committed in tests/golden/tapgemm_isa.sha256 and checked by
+    tests/test_abi.py — a kernel edit has to refresh it (`python tools/check_isa.py --update-hash`) and, with it, rerun the
+    GPU parity cases."""
+    code, _, meta = asm_text.partition("\n\t.amdgpu_metadata\n")
+    streams, cur = {}, None
+    for l in code.split("\n"):
+        l = l.split(";")[0].strip()
+        m = re.match(r"\.type\s+(\S+),@function", l)
+        if m:
+            cur = streams.setdefault(m.group(1), [])
+        elif l.startswith(".Lfunc_end"):
+            cur = None
+        if not l or l.startswith(".") or l.endswith(":") or l.startswith("__hip_cuid"):
+            continue
+        if cur is None:                      # an instruction outside every function
+            cur = streams.setdefault("<module>", [])
+        cur.append(re.sub(r"\.LBB\d+_", ".LBB_", " ".join(l.split())))
+    # metadata: one list item per kernel under `amdhsa.kernels:` (two-space indent), named by its four-space `.name:` key
+    for item in re.split(r"\n(?=  - )|\n(?=\S)", meta.split("\n\t.end_amdgpu_metadata")[0]):
+        name = re.search(r"^    \.name:\s+(\S+)", item, re.M) if item.startswith("  - ") else None
+        streams.setdefault(name.group(1) if name else "<module>", []).extend(" ".join(l.split()) for l in item.split("\n") if l.strip())
+    table = {k: (hashlib.sha256("\n".join(v).encode()).hexdigest(), len(v)) for k, v in streams.items()}
+    pairs = "\n".join(f"{k} {table[k][0]}" for k in sorted(table))
+    return hashlib.sha256(pairs.encode()).hexdigest(), table
+
+
+def isa_moved(table, pinned) -> list:
+    """Names of the kernels whose stream hash differs between a fingerprint table and a pinned {kernel: sha256}, each with
+    what happened to it."""
+    return sorted([f"{k} (changed)" for k in table if k in pinned and table[k][0] != pinned[k]] +
+                  [f"{k} (new)" for k in table if k not in pinned] + [f"{k} (gone)" for k in pinned if k not in table])
+
+
+def read_isa_pin(path: str):
+    """tests/golden/tapgemm_isa.sha256 -> (digest, compiler line or None, {kernel: sha256})"""
+    lines = open(path).read().split("\n")
+    cc = next((l.split(":", 1)[1].strip() for l in lines[1:] if l.startswith("hipcc:")), None)
+    return lines[0].strip(), cc, dict(l.split()[::-1] for l in lines[1:] if l and not l.startswith("hipcc:"))
 
 
 if __name__ == "__main__":

@@ -42,5 +42,17 @@ int vgen_device_cus() {
   return cus[d];
 }
 
+int vgen_lds_optin(const void* kernel, size_t bytes, bool* done, const char* name) {
+  const int dev = vgen_device_slot();
+  if (done[dev]) return 0;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) {
+    vgen_set_error("%s: hipFuncSetAttribute(%zu B LDS) failed: %s", name, bytes, hipGetErrorString(e));
+    return (int)e;
+  }
+  done[dev] = true;
+  return 0;
+}
+
 extern "C" int vgen_version(void) { return VGEN_ABI_VERSION; }
 extern "C" const char* vgen_last_error(void) { return g_err; }

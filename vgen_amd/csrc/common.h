@@ -210,3 +210,6 @@ static inline bool vgen_aligned16(const void* p) { return (((uintptr_t)p) & 15u)
 constexpr int VGEN_MAX_DEVICES = 16;
 int vgen_device_slot();
 int vgen_device_cus();
+// The opt-in to more than 64 KiB of dynamic LDS, once per kernel and device: `done` is the kernel's own
+// `static bool done[VGEN_MAX_DEVICES]`.  0, or the hipError_t with vgen_last_error() naming the kernel and the size.
+int vgen_lds_optin(const void* kernel, size_t bytes, bool* done, const char* name);

@@ -849,19 +849,10 @@ static int groupnorm_impl(const float* x1, int32_t C1, const float* cs1, const f
     const int cpg = C / groups;
     if (nb * S * C * 4 <= fused_max && cpg % 2 == 0 && C1 % 2 == 0 && cpg / 2 <= GNF_THREADS && S * cpg <= GNF_LDS_FLOATS) {
       const size_t lds = (size_t)S * cpg * sizeof(float);
-      static bool attr_done_dev[VGEN_MAX_DEVICES] = {false};
-      bool& attr_done = attr_done_dev[vgen_device_slot()];
-      if (!attr_done) {
-        hipError_t e1 = hipFuncSetAttribute((const void*)gn_fused_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            GNF_LDS_FLOATS * 4);
-        hipError_t e2 = hipFuncSetAttribute((const void*)gn_fused_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            GNF_LDS_FLOATS * 4);
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-          vgen_set_error("groupnorm: hipFuncSetAttribute(LDS) failed");
-          return VGEN_E_BADARG;
-        }
-        attr_done = true;
-      }
+      static bool done_bf16[VGEN_MAX_DEVICES] = {false}, done_f16[VGEN_MAX_DEVICES] = {false};
+      if (vgen_lds_optin((const void*)gn_fused_kernel<BF16>, GNF_LDS_FLOATS * 4, done_bf16, "groupnorm") ||
+          vgen_lds_optin((const void*)gn_fused_kernel<F16>, GNF_LDS_FLOATS * 4, done_f16, "groupnorm"))
+        return VGEN_E_BADARG;
       dim3 fgrid((unsigned)groups, (unsigned)nb);
       if (dtype == VGEN_BF16) {
         hipLaunchKernelGGL(gn_fused_kernel<BF16>, fgrid, dim3(GNF_THREADS), lds, s, x1, C1, x2, C2, S, groups, eps,

@@ -30,6 +30,7 @@
 // 57344 x 2560 x 320 175 -> 118 us, q/k/v 57344 x 960 x 320 85 -> 64 us (dual-W 114 -> 86), out-projection with fp32
 // residual 55 -> 49 us (HBM-bound: 183 MB), whole t2v step -4 % in same-box A/Bs.
 #include "common.h"
+#include "tapgemm_plan.h"   // vgen_panel_bn: which launches take this shape, and the panel width
 
 #include <stdlib.h>
 #include <type_traits>
@@ -85,7 +86,6 @@ constexpr int SLICE_ROWS = 32;
 // x 64 cycles: head start of waves 0-3 over their SIMD partners 4-7.  Scanned 0 ... 128 per shape on the GPU
 // (profiles/r05g_panel_stagger.json): GEGLU 138 -> 118 us at 64, q / qkv -4 ... -5 %, the HBM-bound fp32 launches +-1 %.
 constexpr int PANEL_STAGGER = 64;
-constexpr bool PANEL_K640 = true;     // K = 640 launches (80-column single-pass panels) take this shape too
 
 enum { EPI_F32 = 0, EPI_16 = 1, EPI_GEGLU16 = 2 };   // fp32 store | 16-bit store | GEGLU gate + 16-bit store
 
@@ -356,17 +356,8 @@ template <typename T, int KS, int BN, bool DW, int EPI>
 int launch_panel(const vgen_tapgemm_args& a, hipStream_t stream) {
   constexpr int LROWS = DW ? 2 * BN : BN;
   constexpr size_t lds = (size_t)(KS / 2) * LROWS * 128 + BN * sizeof(float) + PANEL_WAVES * 3 * 2048;   // panel | bias | A rings
-  static bool attr_done[VGEN_MAX_DEVICES] = {false};   // the opt-in is per device
-  const int dev = vgen_device_slot();
-  if (!attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)panel_kernel<T, KS, BN, DW, EPI>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      vgen_set_error("tapgemm(panel): hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_done[dev] = true;
-  }
+  static bool attr_done[VGEN_MAX_DEVICES] = {false};
+  if (const int rc = vgen_lds_optin((const void*)panel_kernel<T, KS, BN, DW, EPI>, lds, attr_done, "tapgemm(panel)")) return rc;
   const int P = a.N / BN;
   int Cn = vgen_device_cus() / P;                            // one block per CU: row ranges x panels <= the device's CUs
   const int nslices = (int)((a.M + SLICE_ROWS - 1) / SLICE_ROWS);
@@ -382,35 +373,6 @@ int launch_panel(const vgen_tapgemm_args& a, hipStream_t stream) {
 }
 
 }  // namespace
-
-// K = 640 panels: on by default once measured; the tuning build can switch them off (VGEN_PANEL_K640=0) for the A/B
-static bool panel640_enabled() {
-#ifdef VGEN_TUNING
-  if (const char* e = getenv("VGEN_PANEL_K640")) return atoi(e) != 0;
-#endif
-  return PANEL_K640;
-}
-
-// which launches take the panel shape (host side; tapgemm.hip's dispatch asks before it plans a streaming shape):
-// the column-panel width, 0 = not this shape
-int vgen_panel_bn(const vgen_tapgemm_args& a) {
-  const bool geglu = a.epilogue == VGEN_EPI_GEGLU;
-  if (a.mode != VGEN_TAP_LINEAR || a.taps != 1 || a.C2 != 0 || (a.C1 != 320 && a.C1 != 640)) return 0;
-  if (a.rowbias || a.colstats || a.split_out) return 0;
-  if (a.M < 2048) return 0;                                  // a handful of slices per CU: the streaming shapes' split-K wins
-  if (a.out_dtype == VGEN_F32 ? (a.ldo % 4 != 0 || geglu) : (a.ldo % 8 != 0)) return 0;
-  if (a.residual && a.ldr % 4 != 0) return 0;
-  int bn;
-  if (a.C1 == 640) {
-    // K = 640 (the 16 x 28 level): an 80-row single-pass panel is the 100 KiB; no dual-W, no GEGLU (40 / 64-column panels
-    // would re-read A 2-4 x as often as the streaming tiles do)
-    if (a.dualw || geglu || !panel640_enabled()) return 0;
-    bn = 80;
-  } else {
-    bn = a.dualw ? (geglu ? 64 : 80) : 160;
-  }
-  return a.N % bn == 0 ? bn : 0;
-}
 
 template <typename T>
 static int panel_dispatch(const vgen_tapgemm_args& a, hipStream_t s) {

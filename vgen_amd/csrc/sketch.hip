@@ -574,17 +574,9 @@ extern "C" int vgen_cdcm_head(const void* t, int64_t ldt, int64_t n, int32_t H, 
   p.Wd = (const uint16_t*)Wd; p.Wa = Wa; p.ba = ba; p.wr = wr; p.out = out; p.ldo = ldo;
   const int64_t grid = n * p.tiles_x * p.tiles_y;
   VGEN_REQUIRE(grid < (1LL << 31), "cdcm_head: too large");
-  static bool attr_done[VGEN_MAX_DEVICES] = {false};   // the LDS opt-in is per device
-  const int dev = vgen_device_slot();
-  if (!attr_done[dev]) {
-    hipError_t e1 = hipFuncSetAttribute((const void*)cdcm_head_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_LDS);
-    hipError_t e2 = hipFuncSetAttribute((const void*)cdcm_head_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_LDS);
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-      vgen_set_error("cdcm_head: hipFuncSetAttribute(%d B LDS) failed", CD_LDS);
-      return (int)(e1 != hipSuccess ? e1 : e2);
-    }
-    attr_done[dev] = true;
-  }
+  static bool done_bf16[VGEN_MAX_DEVICES] = {false}, done_f16[VGEN_MAX_DEVICES] = {false};
+  if (const int rc = vgen_lds_optin((const void*)cdcm_head_kernel<BF16>, CD_LDS, done_bf16, "cdcm_head")) return rc;
+  if (const int rc = vgen_lds_optin((const void*)cdcm_head_kernel<F16>, CD_LDS, done_f16, "cdcm_head")) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (dtype == VGEN_BF16)
     hipLaunchKernelGGL(cdcm_head_kernel<BF16>, dim3((unsigned)grid), dim3(256), CD_LDS, s, p);

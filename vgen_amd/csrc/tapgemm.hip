@@ -6,12 +6,10 @@
 //     channels-last row layout every tap's K-slab is one contiguous C-length row of a shifted
 //     pixel / frame, so a conv A-tile is a row GATHER of 128-byte pieces — no im2col buffer,
 //     no torch.cat, no F.interpolate, no rearrange.
-//   * one kernel template, three block shapes chosen per launch by make_plan() (table further down):
-//     "pp" 256 x BN, BK 64, 8 waves, one block per CU, ping-pong wave groups; "dual" 256 x BN, BK 32,
-//     4 waves with 128-row wave tiles, two blocks per CU; "pp128" 128 x BN for under-filled launches.
-//     BN = 128 (N % 128 == 0), 160 (N = 320 / 960 ...: exact tiles instead of 2.5 x 128) or 64
-//     (small / odd N); 16x16x32 MFMA fragments.  256-row tiles halve the L2->LDS bytes per flop of a
-//     128 x 128 tile (85-98 flop/B).
+//   * one kernel template in five block shapes (256- and 128-row tiles, 8-wave ping-pong or two independent 4-wave
+//     blocks per CU, BN = 128 / 160 / 64 / 256), described ONCE in the shape table of tapgemm_plan.h and chosen per launch
+//     by the planner (tapgemm_plan.cpp, host-only); 16x16x32 MFMA fragments.  256-row tiles halve the L2->LDS bytes per
+//     flop of a 128 x 128 tile (85-98 flop/B).
 //   * operands swapped on the matrix core: D[i = n][j = m] = sum_k W[n,k] * A[m,k].  The
 //     C/D fragment then holds 4 CONSECUTIVE n for one m per lane -> bias / residual / output
 //     move as one 16-byte (fp32) or 8-byte (16-bit) vector per fragment.
@@ -36,27 +34,16 @@
 //     + fp32 residual, optional GEGLU gate, fp32 or 16-bit store, optional per-64-row-slab column
 //     statistics for the GroupNorm that consumes the output.
 #include "common.h"
+#include "tapgemm_plan.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
-// panelgemm.hip: the W-panel-resident shape of the short-K (K = 320) linears; vgen_panel_bn() = its column-panel width for
-// a launch it takes, 0 for every other launch
-int vgen_panel_bn(const vgen_tapgemm_args& a);
+// panelgemm.hip: the W-panel-resident shape of the short-K (K = 320 / 640) linears
 int vgen_panel_launch(const vgen_tapgemm_args& a, hipStream_t s);
 
 namespace {
 
-// Two block shapes of ONE kernel template (BM x BN tile, BK K-elements per stage, WM x WN waves):
-//   "pp"   256 x BN, BK = 64, 4x2 waves (512 threads), 3-stage ring, ONE block per CU, ping-pong wave
-//          groups (below) — the long-K shape: convs, big linears.
-//   "dual" 256 x BN, BK = 32, 2x2 waves (256 threads, wave tile 128 x BN/2), 3-stage ring of 24-26 KiB
-//          stages, TWO blocks per CU (<= 80 KiB LDS, <= 256 VGPRs each).  The two blocks are not
-//          barrier-coupled: one block's prologue (index math, first DMA latency), fragment reads and
-//          epilogue (GELU, residual traffic, stores) run under the other's MFMAs.  The short-K
-//          linears of the transformer blocks (5-20 K-steps per tile) spend 60-80 % of a "pp" tile in
-//          exactly those phases (ablation in profiles/).  The 128-row wave tile also reads 25 % fewer
-//          LDS bytes per MFMA than the 64 x 64 one.
 struct RowState {
   int base;  // LINEAR/TEMPORAL: source row m; CONV: img * Hi * Wi
   int a;     // CONV: iy0 ; TEMPORAL: frame index
@@ -65,13 +52,7 @@ struct RowState {
 
 constexpr int INVALID = -(1 << 24);
 
-// Source of padding / out-of-range rows: a zero REGION long enough for a pointer to walk a whole K extent through it
-// (K * 2 bytes — twice that on the W side of a dual-W launch — <= 256 KiB - 128, checked on the host), so every DMA
-// source pointer advances by the same ROW_BYTES per K-tile whether its row is live or not — no per-piece increment
-// registers (7 VGPRs on the dual shape, which sat at 256 VGPRs with 3 spills).  256 KiB: K <= 131008 for a plain
-// launch, <= 65504 with dual-W — the VAE's P.V product over a 90 x 160 latent (K = 14400) and the widest decoder
-// conv of the UNet (K = 9 * 2560, dual-W) fit with room (r02's 64 KiB bound did not: ADVICE r02).
-constexpr int ZERO_BYTES = 262144;
+// the zero region padding / out-of-range rows are read from (ZERO_BYTES: tapgemm_plan.h)
 __device__ __attribute__((aligned(128))) unsigned char g_zeros[ZERO_BYTES];
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -757,7 +738,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN == 4) ? 2 : 1) void tapgemm_k
     }
     return;
   }
-  // "pp256" (NF = 8, 64 x 128 wave tiles): planned for 16-bit outputs only (legal() below) — the fp32 / column-statistics
+  // "pp256" (NF = 8, 64 x 128 wave tiles): planned for 16-bit outputs only (legal() in tapgemm_plan.cpp) — the fp32 / column-statistics
   // epilogue is not instantiated for it (its cs_s / cs_q / bias registers next to 128 accumulators spilled 320 VGPRs)
   if constexpr (NF > 5) return;
   // column statistics of the final fp32 values per 64-row slab (vgen_tapgemm_args.colstats): the wave
@@ -928,26 +909,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const vgen_tapgemm_a
   else *(u32x2*)((uint16_t*)p.out + m * p.ldo + j) = pack4<T>(v.x, v.y, v.z, v.w);
 }
 
-// ---- launch planning ---------------------------------------------------------------------------
-// 256-row tiles make tile-count quantisation expensive (280 tiles on 256 CUs = 2 rounds at 55 %
-// fill), so the block shape, the column tile BN and the split-K factor are chosen together from a
-// small cost model (microseconds; constants fitted to profiles/r01_*_tapgemm_shapes.json):
-//   cost = rounds(tiles * s / slots) * (ceil(KT / s) * t_ktile + t_tile) + [s > 1] * reduce(s)
-// with KT in 64-element K-steps, slots = 256 ("pp", one block per CU) or 512 ("dual").
-// r06 shapes (never proposed by the cost model: reached through the measured plan table / forced plans only):
-//   "pp256" 256 x 256, BK 32, 8 waves (64 x 128 wave tiles), ping-pong, 3 x 32 KiB ring: 128 FLOP per staged byte instead of
-//           85-98 — for the N % 256 == 0 launches with 16-bit outputs (GEGLU up-projections, the K = 1280 q/k/v); 214 VGPRs.
-//   "q128"  128 x BN, BK 32, 4 waves (64 x BN/2 wave tiles), lock-step K-steps, 3 x (128 + BN) x 64 B ring (48-55 KiB):
-//           2 INDEPENDENT blocks per CU — for the under-filled 8 x 14 / 4 x 7 levels, where one 8-wave block per CU
-//           leaves every stall of its short K loop uncovered.  (Bounded to three blocks per CU the 128 x 128 instance
-//           spilled 16 VGPRs in its epilogue: two, like the dual shape.)
-enum Shape { SHAPE_PP = 0, SHAPE_DUAL = 1, SHAPE_PP128 = 2, SHAPE_PANEL = 3, SHAPE_PP256 = 4, SHAPE_Q128 = 5 };
-// r04: 224-row tiles (every row count of the t2v UNet is 7 * 2^k, so 256-row tiles fill the last round over the CUs at
-// most 87.5 %) were built as a dual 224 x BN shape and a 224 x 320 ping-pong shape, passed every parity case they are legal
-// for, and measured +0.5 % (mixed) / +1.4 % (single-pass) SLOWER on the whole step in a same-box A/B
-// (profiles/r04a_ab_libs.jsonl); so was the buffer-resource LDS-DMA (+0.1 / +0.6 %).  Both were removed again (history:
-// commits 34443ca, 6b9d39a).
-
 // start stagger of the streaming shapes (see tapgemm_kernel): per cent of one tile's estimated time, by blocks per CU, and the
 // fewest rounds of tiles a launch must have; measured on the whole step (profiles/r06b_ab_stagger.jsonl)
 // r06 call B, one process, 8 settings x 3 interleaved rounds (profiles/r06b_ab_stagger.jsonl, r06b_ab_stagger_shapes.json):
@@ -959,154 +920,17 @@ constexpr int STAGGER_PCT_PP = 50;
 constexpr int STAGGER_PCT_DUAL = 50;
 constexpr int STAGGER_MIN_ROUNDS = 2;
 
-struct Plan {
-  int shape;
-  int bn;
-  int splitk;
-};
-
-#ifdef VGEN_TUNING
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-#endif
-
-// Measured plans for the launches of the reference's t2v UNet at its benchmark shape (tools/autotune_gemm.py
-// times every (shape, BN, split-K) candidate per distinct launch signature on the GPU and writes this table):
-// consulted before the cost model, which stays the rule for every other shape.
-struct PlanEntry {
-  int mode;
-  int64_t M;
-  int N, C1, C2, taps, epilogue, out_dtype, flags;   // flags: residual | rowbias << 1 | colstats << 2
-  int shape, bn, splitk;
-};
-#include "tapgemm_plans.inc"
-
-// the active table: the compiled-in one, or whatever vgen_tapgemm_set_plans installed (tools/autotune_gemm.py
-// A/B-tests a candidate table inside one process before it is baked into tapgemm_plans.inc)
-PlanEntry* g_plans = nullptr;
-int g_nplans = -1;
-
-Plan make_plan(const vgen_tapgemm_args& a, bool* from_table = nullptr) {
-  if (from_table) *from_table = false;
-  const bool geglu = a.epilogue == VGEN_EPI_GEGLU;
-  const int KT = a.taps * (a.C1 / 64) + a.C2 / 64;
-  const int n_out = geglu ? a.N / 2 : a.N;
-  const bool vec = (a.N % 4 == 0) && (n_out % 4 == 0) && (a.ldo % 4 == 0) &&
-                   (a.residual == nullptr || a.ldr % 4 == 0) &&
-                   (a.rowbias == nullptr || a.rowbias_ld % 4 == 0);
-  int cands[2], nc = 0;
-  if (a.N % 128 == 0) cands[nc++] = 128;
-  if (a.N % 160 == 0 && !geglu) cands[nc++] = 160;
-  if (nc == 0) cands[nc++] = 64;
-  // tuning build only (not part of the ABI): VGEN_TAPGEMM_SHAPE = 0 (pp) / 1 (dual) / 2 (pp128) forces a shape
-#ifdef VGEN_TUNING
-  static const int force_shape = env_int("VGEN_TAPGEMM_SHAPE", -1);
-#else
-  constexpr int force_shape = -1;
-#endif
-  const int smax = (vec && a.colstats == nullptr && !a.split_out) ? (KT / 4 < 32 ? KT / 4 : 32) : 1;
-  // HBM time of the epilogue traffic (output + fp32 residual), not hidden behind MFMAs when every CU
-  // runs one block in the same phase ("pp"); about half hidden with two independent blocks per CU
-  const double epi_us = (double)a.M * n_out * ((a.out_dtype == VGEN_F32 ? 4 : 2) + (a.residual ? 4 : 0)) / 4.5e6;
-  auto legal = [&](int shape, int bn, int sk) {
-    // BN = 64 is legal for any N as a forced / tabled plan (small-M levels: more, smaller tiles instead of split-K);
-    // the cost model itself only proposes it when neither 128 nor 160 divides N
-    if (sk < 1 || sk > (smax < 1 ? 1 : smax)) return false;
-    if (shape == SHAPE_PP256)   // its own epilogue: 16-bit outputs through the paired 16-byte stores only; with split-K the
-                                // reducer launch holds the epilogue, so any output the reducer takes is legal
-      return bn == 256 && a.N % 256 == 0 && vec && !a.colstats && !a.dualw && !a.split_out &&
-             (sk > 1 || (a.out_dtype != VGEN_F32 && a.ldo % 8 == 0));
-    bool ok = bn == 64 && a.N % 64 == 0 && (!geglu || a.N % 64 == 0);
-    for (int c = 0; c < nc; ++c) ok |= cands[c] == bn;
-    if (shape == SHAPE_Q128) return ok && !a.dualw;
-    return ok && shape >= SHAPE_PP && shape <= SHAPE_PP128 &&
-           !(a.colstats && shape == SHAPE_PP128) && !(a.dualw && shape == SHAPE_DUAL);
-  };
-#ifdef VGEN_TUNING
-  // tuning build only: VGEN_TAPGEMM_PLAN="shape,bn,splitk" forces one plan (read on every call: the autotuner flips
-  // it between launches); VGEN_TAPGEMM_TABLE=0 ignores the measured table
-  if (const char* fp = getenv("VGEN_TAPGEMM_PLAN")) {
-    int sh = -1, bn = 0, sk = 0;
-    if (sscanf(fp, "%d,%d,%d", &sh, &bn, &sk) == 3 && legal(sh, bn, sk)) return Plan{sh, bn, sk};
-  }
-  static const bool use_table = env_int("VGEN_TAPGEMM_TABLE", 1) != 0;
-#else
-  constexpr bool use_table = true;
-#endif
-  if (use_table && force_shape < 0 && !a.dualw) {
-    const int flags = (a.residual ? 1 : 0) | (a.rowbias ? 2 : 0) | (a.colstats ? 4 : 0);
-    const PlanEntry* tab = g_nplans >= 0 ? g_plans : kPlans;
-    const int ntab = g_nplans >= 0 ? g_nplans : (int)(sizeof(kPlans) / sizeof(kPlans[0]));
-    for (int i = 0; i < ntab; ++i) {
-      const PlanEntry& e = tab[i];
-      if (e.mode == a.mode && e.M == a.M && e.N == a.N && e.C1 == a.C1 && e.C2 == a.C2 && e.taps == a.taps &&
-          e.epilogue == a.epilogue && (e.out_dtype == VGEN_F32) == (a.out_dtype == VGEN_F32) && e.flags == flags &&
-          legal(e.shape, e.bn, e.splitk)) {   // out_dtype: fp32 vs 16-bit (bf16 and fp16 launches share an entry)
-        if (from_table) *from_table = true;
-        return Plan{e.shape, e.bn, e.splitk};
-      }
-    }
-  }
-  Plan best{SHAPE_PP, cands[0], 1};
-  double best_cost = 1e30;
-  for (int shape = SHAPE_PP; shape <= SHAPE_PP128; ++shape) {
-    if (force_shape >= 0 && shape != force_shape && !(a.colstats && force_shape == SHAPE_PP128)) continue;
-    if (a.colstats && shape == SHAPE_PP128) continue;   // 32-row wave tiles: a slab would span two waves
-    if (a.dualw && shape == SHAPE_DUAL) continue;       // dual-W K-steps exist on the ping-pong shapes only
-    const int bm = shape == SHAPE_PP128 ? 128 : 256;
-    const int64_t tiles_m = (a.M + bm - 1) / bm;
-    for (int c = 0; c < nc; ++c) {
-      const int bn = cands[c];
-      const int bi = bn == 128 ? 0 : (bn == 160 ? 1 : 2);
-      // us per 64-element K-step of one block: pp alone on its CU; dual alone / sharing the CU
-      static const double t_pp[3] = {0.85, 1.15, 0.60};
-      static const double t_d1[3] = {1.10, 1.30, 0.75};
-      static const double t_d2[3] = {2.20, 2.50, 1.40};
-      static const double t_p128[3] = {0.62, 0.80, 0.45};
-      const int64_t tiles = tiles_m * ((a.N + bn - 1) / bn);
-      for (int s = 1; s <= (smax < 1 ? 1 : smax); ++s) {
-        const int64_t blocks = tiles * s;
-        const int kts = (KT + s - 1) / s;
-        // a dual-W pair = an ordinary K-step + an odd step that reads 10 of 18 fragments and issues 3 of 7 DMA pieces
-        const double dwf = a.dualw ? 1.6 : 1.0;
-        double cost;
-        if (shape == SHAPE_PP) {
-          cost = (double)((blocks + 255) / 256) * (kts * dwf * t_pp[bi] + 8.0) + epi_us;
-        } else if (shape == SHAPE_PP128) {
-          cost = (double)((blocks + 255) / 256) * (kts * dwf * t_p128[bi] + 6.0) + epi_us;
-        } else if (blocks <= 256) {
-          cost = kts * t_d1[bi] + 10.0 + epi_us;
-        } else {
-          cost = (double)((blocks + 511) / 512) * (kts * t_d2[bi] + 9.0) + 0.5 * epi_us + 1.0;
-        }
-        if (s > 1) cost += 5.0 + (double)(s + 1) * a.M * a.N * 4.0 / 3.0e6;   // partials at ~3 TB/s
-        if (cost < best_cost - 1e-9) {
-          best_cost = cost;
-          best = Plan{shape, bn, s};
-        }
-      }
-    }
-  }
-  return best;
-}
-
-template <typename T, int BM, int BN, int BK, int WM, int WN, int STAGES, bool PP, bool DW = false>
+// One launch of the streaming kernel in block shape S (a row of kShapes, tapgemm_plan.h) with column tile BN.
+template <typename T, int S, int BN, bool DW>
 int launch(const vgen_tapgemm_args& a, int splitk, hipStream_t stream) {
+  constexpr ShapeDesc d = kShapes[S];
+  constexpr int BM = d.bm, BK = d.bk, WM = d.wm, WN = d.wn, STAGES = 3;
+  constexpr int BPC = d.bpc;                       // co-resident blocks per CU
+  static_assert(BPC == ((WM * WN == 4) ? 2 : 1), "kShapes' blocks per CU is the kernel's __launch_bounds__ rule");
+  const auto kernel = tapgemm_kernel<T, BM, BN, BK, WM, WN, STAGES, d.pp, DW>;
   constexpr size_t lds = (size_t)STAGES * (BM + BN) * BK * 2;
-  static bool attr_done[VGEN_MAX_DEVICES] = {false};   // the opt-in is per device
-  const int dev = vgen_device_slot();
-  if (!attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)tapgemm_kernel<T, BM, BN, BK, WM, WN, STAGES, PP, DW>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      vgen_set_error("tapgemm: hipFuncSetAttribute(%zu B LDS) failed: %s", lds,
-                     hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_done[dev] = true;
-  }
+  static bool attr_done[VGEN_MAX_DEVICES] = {false};
+  if (const int rc = vgen_lds_optin((const void*)kernel, lds, attr_done, "tapgemm")) return rc;
   const int64_t tiles_m = (a.M + BM - 1) / BM;
   const int64_t tiles_n = (a.N + BN - 1) / BN;
   const int64_t grid = tiles_m * tiles_n;
@@ -1117,15 +941,16 @@ int launch(const vgen_tapgemm_args& a, int splitk, hipStream_t stream) {
   }
   if (splitk > 1 && (a.ws == nullptr || a.ws_bytes < (size_t)splitk * a.M * a.N * sizeof(float)))
     splitk = 1;   // caller did not provide the workspace: still correct, just fewer blocks
+  // launch-side switches of the tuning build: VGEN_TAPGEMM_ABLATE (see the kernel), VGEN_TAPGEMM_STAGGER = "pct of a tile
+  // for one block per CU, for two[, fewest rounds]"
 #ifdef VGEN_TUNING
   const char* ab = getenv("VGEN_TAPGEMM_ABLATE");
   const int ablate = ab ? atoi(ab) : 0;
 #else
   const int ablate = 0;
 #endif
-  // start stagger (see the kernel): a fraction of the estimated time of one tile (the cost model's constants), only for
-  // launches with enough rounds of tiles to win it back
-  constexpr int BPC = (WM * WN == 4) ? 2 : 1;      // co-resident blocks per CU
+  // start stagger (see the kernel): a fraction of the estimated time of one tile, only for launches with enough rounds of
+  // tiles to win it back
   const int cus = vgen_device_cus();
   int stagger = 0;
   {
@@ -1142,198 +967,54 @@ int launch(const vgen_tapgemm_args& a, int splitk, hipStream_t stream) {
     const int64_t blocks = grid * splitk;
     const double rounds = (double)blocks / ((double)cus * BPC);
     if (pct > 0 && rounds >= (double)min_rounds) {
-      const int KT = a.taps * (a.C1 / 64) + a.C2 / 64;
-      const int kts = (KT + splitk - 1) / splitk;
-      const double tile_us = kts * (a.dualw ? 1.6 : 1.0) * (BM == 256 ? (BPC == 1 ? 0.0060 * BN : 0.0150 * BN) : 0.0050 * BN) + 7.0;
+      const int kts = (tap_kt(a) + splitk - 1) / splitk;
+      const double tile_us = kts * (a.dualw ? DUALW_KSTEP_FACTOR : 1.0) * (d.stagger_us * BN) + 7.0;
       stagger = (int)(tile_us * pct / 100.0 * 2400.0 / 1024.0 + 0.5);
     }
   }
-  hipLaunchKernelGGL((tapgemm_kernel<T, BM, BN, BK, WM, WN, STAGES, PP, DW>), dim3((unsigned)grid, (unsigned)splitk),
-                     dim3(WM * WN * 64), lds, stream, a, splitk, (float*)a.ws, ablate, stagger, cus * BPC);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid, (unsigned)splitk), dim3(WM * WN * 64), lds, stream, a, splitk, (float*)a.ws,
+                     ablate, stagger, cus * BPC);
   int rc = vgen_check_launch("tapgemm");
   if (rc || splitk == 1) return rc;
-  const int n_out = a.epilogue == VGEN_EPI_GEGLU ? a.N / 2 : a.N;
-  const int64_t threads = a.M * (n_out / 4);
+  const int64_t threads = a.M * (tap_n_out(a) / 4);
   hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
                      stream, a, splitk, (const float*)a.ws);
   return vgen_check_launch("tapgemm(splitk reduce)");
 }
 
-// the panel shape is asked first: a launch it takes is never planned on a streaming shape (tuning build:
-// VGEN_TAPGEMM_PANEL=0 sends everything to the streaming shapes — the same-box A/B of the two)
-int panel_bn(const vgen_tapgemm_args& a) {
-#ifdef VGEN_TUNING
-  if (env_int("VGEN_TAPGEMM_PANEL", 1) == 0) return 0;
-#endif
-  return vgen_panel_bn(a);
-}
-
-// The plan of a launch: a measured table entry first (r06: it may also take a K = 320 / 640 linear AWAY from the panel shape),
-// then the panel shape for the launches it takes, then the cost model.
-Plan full_plan(const vgen_tapgemm_args& a) {
-  bool tabled = false;
-  const Plan pl = make_plan(a, &tabled);
-  if (!tabled)
-    if (const int bn = panel_bn(a)) return Plan{SHAPE_PANEL, bn, 1};
-  return pl;
+// the one switch over the column tile
+template <typename T, int S, bool DW>
+int launch_bn(const vgen_tapgemm_args& a, const Plan& pl, hipStream_t s) {
+  switch (pl.bn) {
+    case 128: return launch<T, S, 128, DW>(a, pl.splitk, s);
+    case 160: return launch<T, S, 160, DW>(a, pl.splitk, s);
+    default: return launch<T, S, 64, DW>(a, pl.splitk, s);
+  }
 }
 
 template <typename T>
 int dispatch(const vgen_tapgemm_args& a, hipStream_t s) {
   const Plan pl = full_plan(a);
   if (pl.shape == SHAPE_PANEL) return vgen_panel_launch(a, s);
-  if (a.dualw) {
-    if (pl.shape == SHAPE_PP128) {
-      switch (pl.bn) {
-        case 128: return launch<T, 128, 128, 64, 4, 2, 3, true, true>(a, pl.splitk, s);
-        case 160: return launch<T, 128, 160, 64, 4, 2, 3, true, true>(a, pl.splitk, s);
-        default: return launch<T, 128, 64, 64, 4, 2, 3, true, true>(a, pl.splitk, s);
-      }
-    }
-    switch (pl.bn) {
-      case 128: return launch<T, 256, 128, 64, 4, 2, 3, true, true>(a, pl.splitk, s);
-      case 160: return launch<T, 256, 160, 64, 4, 2, 3, true, true>(a, pl.splitk, s);
-      default: return launch<T, 256, 64, 64, 4, 2, 3, true, true>(a, pl.splitk, s);
-    }
-  }
-  if (pl.shape == SHAPE_PP256) return launch<T, 256, 256, 32, 4, 2, 3, true>(a, pl.splitk, s);
-  if (pl.shape == SHAPE_Q128) {
-    switch (pl.bn) {
-      case 128: return launch<T, 128, 128, 32, 2, 2, 3, false>(a, pl.splitk, s);
-      case 160: return launch<T, 128, 160, 32, 2, 2, 3, false>(a, pl.splitk, s);
-      default: return launch<T, 128, 64, 32, 2, 2, 3, false>(a, pl.splitk, s);
-    }
-  }
-  if (pl.shape == SHAPE_PP) {
-    switch (pl.bn) {
-      case 128: return launch<T, 256, 128, 64, 4, 2, 3, true>(a, pl.splitk, s);
-      case 160: return launch<T, 256, 160, 64, 4, 2, 3, true>(a, pl.splitk, s);
-      default: return launch<T, 256, 64, 64, 4, 2, 3, true>(a, pl.splitk, s);
-    }
-  }
-  if (pl.shape == SHAPE_PP128) {
-    switch (pl.bn) {
-      case 128: return launch<T, 128, 128, 64, 4, 2, 3, true>(a, pl.splitk, s);
-      case 160: return launch<T, 128, 160, 64, 4, 2, 3, true>(a, pl.splitk, s);
-      default: return launch<T, 128, 64, 64, 4, 2, 3, true>(a, pl.splitk, s);
-    }
-  }
-  switch (pl.bn) {
-    case 128: return launch<T, 256, 128, 32, 2, 2, 3, false>(a, pl.splitk, s);
-    case 160: return launch<T, 256, 160, 32, 2, 2, 3, false>(a, pl.splitk, s);
-    default: return launch<T, 256, 64, 32, 2, 2, 3, false>(a, pl.splitk, s);
+  if (a.dualw)   // dual-W K-steps exist on the two 8-wave ping-pong shapes only (the planner plans nothing else for them)
+    return pl.shape == SHAPE_PP128 ? launch_bn<T, SHAPE_PP128, true>(a, pl, s) : launch_bn<T, SHAPE_PP, true>(a, pl, s);
+  switch (pl.shape) {
+    case SHAPE_PP: return launch_bn<T, SHAPE_PP, false>(a, pl, s);
+    case SHAPE_PP128: return launch_bn<T, SHAPE_PP128, false>(a, pl, s);
+    case SHAPE_PP256: return launch<T, SHAPE_PP256, 256, false>(a, pl.splitk, s);
+    case SHAPE_Q128: return launch_bn<T, SHAPE_Q128, false>(a, pl, s);
+    default: return launch_bn<T, SHAPE_DUAL, false>(a, pl, s);
   }
 }
 
 }  // namespace
-
-extern "C" int vgen_tapgemm_query_plan(const vgen_tapgemm_args* args, int32_t* out3) {
-  if (!args || !out3 || args->N <= 0 || args->M <= 0 || args->C1 <= 0 || args->C1 % 64 || args->C2 % 64) return VGEN_E_BADARG;
-  const Plan pl = full_plan(*args);
-  out3[0] = pl.shape;
-  out3[1] = pl.bn;
-  out3[2] = pl.splitk;
-  return 0;
-}
-
-extern "C" int vgen_tapgemm_set_plans(const int64_t* rows, int32_t n) {
-  if (n < 0) {            // back to the compiled-in table
-    free(g_plans);
-    g_plans = nullptr;
-    g_nplans = -1;
-    return 0;
-  }
-  if (n > 0 && !rows) return VGEN_E_BADARG;
-  PlanEntry* t = (PlanEntry*)malloc(sizeof(PlanEntry) * (n > 0 ? n : 1));
-  if (!t) return VGEN_E_BADARG;
-  for (int i = 0; i < n; ++i) {
-    const int64_t* r = rows + 12 * i;
-    t[i] = PlanEntry{(int)r[0], r[1], (int)r[2], (int)r[3], (int)r[4], (int)r[5], (int)r[6], (int)r[7], (int)r[8],
-                     (int)r[9], (int)r[10], (int)r[11]};
-  }
-  free(g_plans);
-  g_plans = t;
-  g_nplans = n;
-  return 0;
-}
-
-extern "C" size_t vgen_tapgemm_ws_bytes(const vgen_tapgemm_args* args) {
-  if (!args || args->N <= 0 || args->M <= 0 || args->C1 <= 0 || args->C1 % 64 || args->C2 % 64) return 0;
-  const int s = full_plan(*args).splitk;
-  return s > 1 ? (size_t)s * args->M * args->N * sizeof(float) : 0;
-}
 
 extern "C" int vgen_tapgemm(const vgen_tapgemm_args* args, void* stream) {
   if (!args) {
     vgen_set_error("tapgemm: null args");
     return VGEN_E_BADARG;
   }
-  const vgen_tapgemm_args& a = *args;
-  VGEN_REQUIRE(a.dtype == VGEN_BF16 || a.dtype == VGEN_F16, "tapgemm: dtype must be bf16/f16");
-  VGEN_REQUIRE(a.M >= 0 && a.N > 0, "tapgemm: bad M/N");
-  VGEN_REQUIRE(a.C1 > 0 && a.C1 % 64 == 0 && a.C2 >= 0 && a.C2 % 64 == 0,
-               "tapgemm: C1=%d / C2=%d must be multiples of 64", a.C1, a.C2);
-  VGEN_REQUIRE(a.dualw == 0 || a.dualw == 1, "tapgemm: dualw must be 0 or 1");
-  VGEN_REQUIRE(a.lda % 8 == 0 && (a.C2 == 0 || a.lda2 % 8 == 0) && a.ldw % 8 == 0 &&
-                   (a.ldw == 0 || a.ldw >= ((int64_t)a.taps * a.C1 + a.C2) * (a.dualw ? 2 : 1)),
-               "tapgemm: lda/lda2/ldw must be multiples of 8 (ldw >= K, 2 K with dualw)");
-  VGEN_REQUIRE(vgen_aligned16(a.A) && vgen_aligned16(a.W) && vgen_aligned16(a.out) &&
-                   (a.C2 == 0 || (a.A2 && vgen_aligned16(a.A2))),
-               "tapgemm: pointers must be 16-byte aligned");
-  VGEN_REQUIRE(a.bias == nullptr || vgen_aligned16(a.bias), "tapgemm: bias alignment");
-  VGEN_REQUIRE(a.residual == nullptr || vgen_aligned16(a.residual), "tapgemm: residual alignment");
-  VGEN_REQUIRE(a.rowbias == nullptr || (vgen_aligned16(a.rowbias) && a.rows_per_rb > 0),
-               "tapgemm: rowbias alignment / rows_per_rb");
-  VGEN_REQUIRE(a.out_dtype == VGEN_F32 || a.out_dtype == a.dtype, "tapgemm: out_dtype");
-  VGEN_REQUIRE(a.ws == nullptr || vgen_aligned16(a.ws), "tapgemm: workspace alignment");
-  switch (a.mode) {
-    case VGEN_TAP_LINEAR:
-      VGEN_REQUIRE(a.taps == 1, "tapgemm: linear mode needs taps == 1");
-      break;
-    case VGEN_TAP_CONV3X3:
-      VGEN_REQUIRE(a.taps == 9 && a.Hi > 0 && a.Wi > 0 && a.Ho > 0 && a.Wo > 0 &&
-                       (a.stride == 1 || a.stride == 2) && (a.ups == 0 || a.ups == 1) && a.crop_t >= 0 &&
-                       (a.crop_t == 0 || a.ups == 1),
-                   "tapgemm: bad conv3x3 geometry");
-      VGEN_REQUIRE(a.M % ((int64_t)a.Ho * a.Wo) == 0, "tapgemm: M not a multiple of Ho*Wo");
-      VGEN_REQUIRE((a.M / ((int64_t)a.Ho * a.Wo)) * a.Hi * a.Wi < (1LL << 31),
-                   "tapgemm: source row index overflows int32");
-      break;
-    case VGEN_TAP_TEMPORAL3:
-      VGEN_REQUIRE(a.taps == 3 && a.F > 0 && a.S > 0 && a.M % (a.S * a.F) == 0,
-                   "tapgemm: bad temporal geometry");
-      break;
-    default:
-      vgen_set_error("tapgemm: unknown mode %d", a.mode);
-      return VGEN_E_BADARG;
-  }
-  VGEN_REQUIRE(a.M + 256 < (1LL << 31), "tapgemm: M overflows int32 row index");
-  VGEN_REQUIRE(a.lda >= 0 && a.lda < (1LL << 30) && a.lda2 >= 0 && a.lda2 < (1LL << 30),
-               "tapgemm: lda / lda2 must be in [0, 2^30)");
-  VGEN_REQUIRE(((int64_t)a.taps * a.C1 + a.C2) * (a.dualw ? 4 : 2) <= ZERO_BYTES - 128,
-               "tapgemm: K = %lld too long (<= 131008; <= 65504 with dualw)",
-               (long long)((int64_t)a.taps * a.C1 + a.C2));
-  if (a.epilogue == VGEN_EPI_GEGLU) {
-    VGEN_REQUIRE(a.N % 64 == 0 && a.rowbias == nullptr && (a.ldo % 4 == 0) &&
-                     (a.residual == nullptr || a.ldr % 4 == 0),
-                 "tapgemm: GEGLU needs N %% 64 == 0, no rowbias, ldo/ldr %% 4 == 0");
-  } else {
-    VGEN_REQUIRE(a.epilogue == VGEN_EPI_NONE, "tapgemm: unknown epilogue");
-  }
-  if (a.colstats) {
-    VGEN_REQUIRE(a.out_dtype == VGEN_F32 && a.epilogue == VGEN_EPI_NONE && a.N % 4 == 0 && a.ldo % 4 == 0 &&
-                     (a.residual == nullptr || a.ldr % 4 == 0) && (a.rowbias == nullptr || a.rowbias_ld % 4 == 0) &&
-                     vgen_aligned16(a.colstats),
-                 "tapgemm: colstats needs fp32 output, no GEGLU, N/ldo/ldr/rowbias_ld %% 4 == 0");
-  }
-  if (a.split_out) {
-    VGEN_REQUIRE(a.split_out == 1 && a.out_dtype != VGEN_F32 && a.epilogue == VGEN_EPI_NONE && a.colstats == nullptr &&
-                     a.N % 32 == 0 && a.ldo % 8 == 0 && a.ldo >= 2 * (int64_t)a.N && (a.residual == nullptr || a.ldr % 4 == 0) &&
-                     (a.rowbias == nullptr || a.rowbias_ld % 4 == 0),
-                 "tapgemm: split_out needs a 16-bit output [M, >= 2 N], no GEGLU / colstats, N %% 32 == 0, ldo %% 8 == 0");
-  }
+  if (const int rc = vgen_tapgemm_validate(*args)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  return a.dtype == VGEN_BF16 ? dispatch<BF16>(a, s) : dispatch<F16>(a, s);
+  return args->dtype == VGEN_BF16 ? dispatch<BF16>(*args, s) : dispatch<F16>(*args, s);
 }
-
-

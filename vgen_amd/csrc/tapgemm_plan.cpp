@@ -1,0 +1,304 @@
+// tapgemm_plan.cpp — the tap-GEMM planner: everything that DECIDES how a vgen_tapgemm launch runs, nothing that launches.
+// Host arithmetic only (no HIP header, no device code): it compiles in seconds, links into a stand-alone program
+// (tests/plan_driver.cpp runs it under the host sanitizers) and an edit here cannot move a kernel instruction.
+//   * argument validation of vgen_tapgemm and the lighter pre-check of the two plan queries;
+//   * the legality rule and the cost model over the shape table of tapgemm_plan.h;
+//   * the measured plan table (tapgemm_plans.inc, or what vgen_tapgemm_set_plans installed);
+//   * which launches take the panel shape of panelgemm.hip;
+//   * the plan-side switches of the tuning build.
+#include "tapgemm_plan.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <new>
+#include <vector>
+
+void vgen_set_error(const char* fmt, ...);   // cabi.cpp (the stand-alone driver brings its own)
+
+// common.h's VGEN_REQUIRE / vgen_aligned16, restated: that header pulls in the HIP runtime
+#define VGEN_REQUIRE(cond, ...)    \
+  do {                             \
+    if (!(cond)) {                 \
+      vgen_set_error(__VA_ARGS__); \
+      return VGEN_E_BADARG;        \
+    }                              \
+  } while (0)
+
+static inline bool vgen_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+namespace {
+
+constexpr bool PANEL_K640 = true;     // K = 640 launches (80-column single-pass panels) take the panel shape too
+
+// Plan-side switches of the TUNING build (-DVGEN_TUNING, libvgen_hip_tuning.so; not part of the ABI) — the product library
+// has the defaults compiled in and reads no environment variable:
+//   VGEN_TAPGEMM_SHAPE = 0 (pp) / 1 (dual) / 2 (pp128)  the cost model proposes this shape only; read ONCE per process
+//   VGEN_TAPGEMM_TABLE = 0                              ignore the measured table; read ONCE per process
+//   VGEN_TAPGEMM_PLAN  = "shape,bn,splitk"              force one plan where it is legal; read on EVERY call (the autotuner
+//                                                       flips it between launches)
+//   VGEN_TAPGEMM_PANEL = 0                              nothing takes the panel shape (same-box A/B of the two); every call
+//   VGEN_PANEL_K640    = 0 / 1                          K = 640 panels off / on; every call
+struct Tuning {
+  int force_shape = -1;
+  bool use_table = true, use_panel = true, panel640 = PANEL_K640, has_plan = false;
+  Plan plan = {-1, 0, 0};
+};
+
+Tuning tuning() {
+  Tuning t;
+#ifdef VGEN_TUNING
+  auto env_int = [](const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+  };
+  static const int force_shape = env_int("VGEN_TAPGEMM_SHAPE", -1);
+  static const bool use_table = env_int("VGEN_TAPGEMM_TABLE", 1) != 0;
+  t.force_shape = force_shape;
+  t.use_table = use_table;
+  t.use_panel = env_int("VGEN_TAPGEMM_PANEL", 1) != 0;
+  t.panel640 = env_int("VGEN_PANEL_K640", PANEL_K640) != 0;
+  if (const char* fp = getenv("VGEN_TAPGEMM_PLAN"))
+    t.has_plan = sscanf(fp, "%d,%d,%d", &t.plan.shape, &t.plan.bn, &t.plan.splitk) == 3;
+#endif
+  return t;
+}
+
+// Measured plans for the launches of the reference's t2v UNet at its benchmark shape (tools/autotune_gemm.py
+// times every (shape, BN, split-K) candidate per distinct launch signature on the GPU and writes this table):
+// consulted before the cost model, which stays the rule for every other shape.
+struct PlanEntry {
+  int mode;
+  int64_t M;
+  int N, C1, C2, taps, epilogue, out_dtype, flags;   // flags: residual | rowbias << 1 | colstats << 2
+  int shape, bn, splitk;
+};
+#include "tapgemm_plans.inc"
+
+// the active table: the compiled-in one, or whatever vgen_tapgemm_set_plans installed (tools/autotune_gemm.py
+// A/B-tests a candidate table inside one process before it is baked into tapgemm_plans.inc)
+std::vector<PlanEntry> g_plans;
+bool g_plans_installed = false;
+
+// ---- launch planning ---------------------------------------------------------------------------
+// 256-row tiles make tile-count quantisation expensive (280 tiles on 256 CUs = 2 rounds at 55 %
+// fill), so the block shape, the column tile BN and the split-K factor are chosen together from a
+// small cost model (microseconds; the constants are kShapes'):
+//   cost = rounds(tiles * s / slots) * (ceil(KT / s) * t_k + t_tile) + [s > 1] * reduce(s)
+// with KT in 64-element K-steps, slots = 256 x blocks per CU.
+Plan make_plan(const vgen_tapgemm_args& a, const Tuning& tune, bool* from_table) {
+  *from_table = false;
+  const bool geglu = a.epilogue == VGEN_EPI_GEGLU;
+  const int KT = tap_kt(a);
+  const int n_out = tap_n_out(a);
+  const bool vec = tap_vec(a);
+  int cands[2], nc = 0;
+  if (a.N % 128 == 0) cands[nc++] = 128;
+  if (a.N % 160 == 0 && !geglu) cands[nc++] = 160;
+  if (nc == 0) cands[nc++] = 64;
+  const int smax = (vec && a.colstats == nullptr && !a.split_out) ? (KT / 4 < 32 ? KT / 4 : 32) : 1;
+  // HBM time of the epilogue traffic (output + fp32 residual), not hidden behind MFMAs when every CU
+  // runs one block in the same phase ("pp"); about half hidden with two independent blocks per CU
+  const double epi_us = (double)a.M * n_out * ((a.out_dtype == VGEN_F32 ? 4 : 2) + (a.residual ? 4 : 0)) / 4.5e6;
+  auto legal = [&](int shape, int bn, int sk) {
+    if (sk < 1 || sk > (smax < 1 ? 1 : smax)) return false;
+    if (shape < 0 || shape >= NUM_SHAPES || shape == SHAPE_PANEL) return false;
+    const ShapeDesc& d = kShapes[shape];
+    if ((a.dualw && !d.dualw) || (a.colstats && !d.colstats)) return false;
+    if (d.out16_only)   // with split-K the reducer launch holds the epilogue, so any output the reducer takes is legal
+      return bn == d.bns[0] && a.N % bn == 0 && vec && !a.split_out && (sk > 1 || (a.out_dtype != VGEN_F32 && a.ldo % 8 == 0));
+    // BN = 64 is legal for any N % 64 == 0 as a forced / tabled plan (small-M levels: more, smaller tiles instead of
+    // split-K); the cost model itself only proposes it when neither 128 nor 160 divides N
+    bool ok = bn == 64 && a.N % 64 == 0;
+    for (int c = 0; c < nc; ++c) ok |= cands[c] == bn;
+    return ok;
+  };
+  if (tune.has_plan && legal(tune.plan.shape, tune.plan.bn, tune.plan.splitk)) return tune.plan;
+  if (tune.use_table && tune.force_shape < 0 && !a.dualw) {
+    const int flags = (a.residual ? 1 : 0) | (a.rowbias ? 2 : 0) | (a.colstats ? 4 : 0);
+    const PlanEntry* tab = g_plans_installed ? g_plans.data() : kPlans;
+    const size_t ntab = g_plans_installed ? g_plans.size() : sizeof(kPlans) / sizeof(kPlans[0]);
+    for (size_t i = 0; i < ntab; ++i) {
+      const PlanEntry& e = tab[i];
+      if (e.mode == a.mode && e.M == a.M && e.N == a.N && e.C1 == a.C1 && e.C2 == a.C2 && e.taps == a.taps &&
+          e.epilogue == a.epilogue && (e.out_dtype == VGEN_F32) == (a.out_dtype == VGEN_F32) && e.flags == flags &&
+          legal(e.shape, e.bn, e.splitk)) {   // out_dtype: fp32 vs 16-bit (bf16 and fp16 launches share an entry)
+        *from_table = true;
+        return Plan{e.shape, e.bn, e.splitk};
+      }
+    }
+  }
+  Plan best{SHAPE_PP, cands[0], 1};
+  double best_cost = 1e30;
+  for (int shape = 0; shape < NUM_SHAPES; ++shape) {
+    const ShapeDesc& d = kShapes[shape];
+    if (!d.modelled) continue;
+    if (tune.force_shape >= 0 && shape != tune.force_shape && !(a.colstats && tune.force_shape == SHAPE_PP128)) continue;
+    if ((a.colstats && !d.colstats) || (a.dualw && !d.dualw)) continue;
+    const int64_t tiles_m = (a.M + d.bm - 1) / d.bm;
+    const int64_t slots = 256 * d.bpc;
+    for (int c = 0; c < nc; ++c) {
+      const int bn = cands[c];
+      const int bi = bn == 128 ? 0 : (bn == 160 ? 1 : 2);
+      const int64_t tiles = tiles_m * ((a.N + bn - 1) / bn);
+      for (int s = 1; s <= (smax < 1 ? 1 : smax); ++s) {
+        const int64_t blocks = tiles * s;
+        const int kts = (KT + s - 1) / s;
+        const double dwf = a.dualw ? DUALW_KSTEP_FACTOR : 1.0;
+        double cost;
+        if (d.bpc == 1) {
+          cost = (double)((blocks + slots - 1) / slots) * (kts * dwf * d.t_k[bi] + d.t_tile) + epi_us;
+        } else if (blocks <= 256) {   // every block alone on its CU
+          cost = kts * d.t_k_alone[bi] + d.t_tile_alone + epi_us;
+        } else {
+          cost = (double)((blocks + slots - 1) / slots) * (kts * d.t_k[bi] + d.t_tile) + 0.5 * epi_us + 1.0;
+        }
+        if (s > 1) cost += 5.0 + (double)(s + 1) * a.M * a.N * 4.0 / 3.0e6;   // partials at ~3 TB/s
+        if (cost < best_cost - 1e-9) {
+          best_cost = cost;
+          best = Plan{shape, bn, s};
+        }
+      }
+    }
+  }
+  return best;
+}
+
+// what the plan queries ask of their argument block before they plan: less than vgen_tapgemm_validate (tools/ query
+// plans for launch signatures without operands)
+bool plannable(const vgen_tapgemm_args* a) {
+  return a && a->N > 0 && a->M > 0 && a->C1 > 0 && a->C1 % 64 == 0 && a->C2 % 64 == 0;
+}
+
+int panel_bn(const vgen_tapgemm_args& a, const Tuning& tune) {
+  const bool geglu = a.epilogue == VGEN_EPI_GEGLU;
+  if (a.mode != VGEN_TAP_LINEAR || a.taps != 1 || a.C2 != 0 || (a.C1 != 320 && a.C1 != 640)) return 0;
+  if (a.rowbias || a.colstats || a.split_out) return 0;
+  if (a.M < 2048) return 0;                                  // a handful of slices per CU: the streaming shapes' split-K wins
+  if (a.out_dtype == VGEN_F32 ? (a.ldo % 4 != 0 || geglu) : (a.ldo % 8 != 0)) return 0;
+  if (a.residual && a.ldr % 4 != 0) return 0;
+  int bn;
+  if (a.C1 == 640) {
+    // K = 640 (the 16 x 28 level): an 80-row single-pass panel is the 100 KiB; no dual-W, no GEGLU (40 / 64-column panels
+    // would re-read A 2-4 x as often as the streaming tiles do)
+    if (a.dualw || geglu || !tune.panel640) return 0;
+    bn = 80;
+  } else {
+    bn = a.dualw ? (geglu ? 64 : 80) : 160;
+  }
+  return a.N % bn == 0 ? bn : 0;
+}
+
+}  // namespace
+
+// panelgemm.hip's own dispatch asks this for its panel width
+int vgen_panel_bn(const vgen_tapgemm_args& a) { return panel_bn(a, tuning()); }
+
+Plan full_plan(const vgen_tapgemm_args& a) {
+  const Tuning tune = tuning();
+  bool tabled = false;
+  const Plan pl = make_plan(a, tune, &tabled);
+  if (!tabled && tune.use_panel)
+    if (const int bn = panel_bn(a, tune)) return Plan{SHAPE_PANEL, bn, 1};
+  return pl;
+}
+
+int vgen_tapgemm_validate(const vgen_tapgemm_args& a) {
+  VGEN_REQUIRE(a.dtype == VGEN_BF16 || a.dtype == VGEN_F16, "tapgemm: dtype must be bf16/f16");
+  VGEN_REQUIRE(a.M >= 0 && a.N > 0, "tapgemm: bad M/N");
+  VGEN_REQUIRE(a.C1 > 0 && a.C1 % 64 == 0 && a.C2 >= 0 && a.C2 % 64 == 0,
+               "tapgemm: C1=%d / C2=%d must be multiples of 64", a.C1, a.C2);
+  VGEN_REQUIRE(a.dualw == 0 || a.dualw == 1, "tapgemm: dualw must be 0 or 1");
+  VGEN_REQUIRE(a.lda % 8 == 0 && (a.C2 == 0 || a.lda2 % 8 == 0) && a.ldw % 8 == 0 &&
+                   (a.ldw == 0 || a.ldw >= ((int64_t)a.taps * a.C1 + a.C2) * (a.dualw ? 2 : 1)),
+               "tapgemm: lda/lda2/ldw must be multiples of 8 (ldw >= K, 2 K with dualw)");
+  VGEN_REQUIRE(vgen_aligned16(a.A) && vgen_aligned16(a.W) && vgen_aligned16(a.out) &&
+                   (a.C2 == 0 || (a.A2 && vgen_aligned16(a.A2))),
+               "tapgemm: pointers must be 16-byte aligned");
+  VGEN_REQUIRE(a.bias == nullptr || vgen_aligned16(a.bias), "tapgemm: bias alignment");
+  VGEN_REQUIRE(a.residual == nullptr || vgen_aligned16(a.residual), "tapgemm: residual alignment");
+  VGEN_REQUIRE(a.rowbias == nullptr || (vgen_aligned16(a.rowbias) && a.rows_per_rb > 0),
+               "tapgemm: rowbias alignment / rows_per_rb");
+  VGEN_REQUIRE(a.out_dtype == VGEN_F32 || a.out_dtype == a.dtype, "tapgemm: out_dtype");
+  VGEN_REQUIRE(a.ws == nullptr || vgen_aligned16(a.ws), "tapgemm: workspace alignment");
+  switch (a.mode) {
+    case VGEN_TAP_LINEAR:
+      VGEN_REQUIRE(a.taps == 1, "tapgemm: linear mode needs taps == 1");
+      break;
+    case VGEN_TAP_CONV3X3:
+      VGEN_REQUIRE(a.taps == 9 && a.Hi > 0 && a.Wi > 0 && a.Ho > 0 && a.Wo > 0 &&
+                       (a.stride == 1 || a.stride == 2) && (a.ups == 0 || a.ups == 1) && a.crop_t >= 0 &&
+                       (a.crop_t == 0 || a.ups == 1),
+                   "tapgemm: bad conv3x3 geometry");
+      VGEN_REQUIRE(a.M % ((int64_t)a.Ho * a.Wo) == 0, "tapgemm: M not a multiple of Ho*Wo");
+      VGEN_REQUIRE((a.M / ((int64_t)a.Ho * a.Wo)) * a.Hi * a.Wi < (1LL << 31),
+                   "tapgemm: source row index overflows int32");
+      break;
+    case VGEN_TAP_TEMPORAL3:
+      VGEN_REQUIRE(a.taps == 3 && a.F > 0 && a.S > 0 && a.M % (a.S * a.F) == 0,
+                   "tapgemm: bad temporal geometry");
+      break;
+    default:
+      vgen_set_error("tapgemm: unknown mode %d", a.mode);
+      return VGEN_E_BADARG;
+  }
+  VGEN_REQUIRE(a.M + 256 < (1LL << 31), "tapgemm: M overflows int32 row index");
+  VGEN_REQUIRE(a.lda >= 0 && a.lda < (1LL << 30) && a.lda2 >= 0 && a.lda2 < (1LL << 30),
+               "tapgemm: lda / lda2 must be in [0, 2^30)");
+  VGEN_REQUIRE(((int64_t)a.taps * a.C1 + a.C2) * (a.dualw ? 4 : 2) <= ZERO_BYTES - 128,
+               "tapgemm: K = %lld too long (<= 131008; <= 65504 with dualw)",
+               (long long)((int64_t)a.taps * a.C1 + a.C2));
+  if (a.epilogue == VGEN_EPI_GEGLU) {
+    VGEN_REQUIRE(a.N % 64 == 0 && a.rowbias == nullptr && (a.ldo % 4 == 0) &&
+                     (a.residual == nullptr || a.ldr % 4 == 0),
+                 "tapgemm: GEGLU needs N %% 64 == 0, no rowbias, ldo/ldr %% 4 == 0");
+  } else {
+    VGEN_REQUIRE(a.epilogue == VGEN_EPI_NONE, "tapgemm: unknown epilogue");
+  }
+  if (a.colstats) {
+    VGEN_REQUIRE(a.out_dtype == VGEN_F32 && a.epilogue == VGEN_EPI_NONE && a.N % 4 == 0 && a.ldo % 4 == 0 &&
+                     (a.residual == nullptr || a.ldr % 4 == 0) && (a.rowbias == nullptr || a.rowbias_ld % 4 == 0) &&
+                     vgen_aligned16(a.colstats),
+                 "tapgemm: colstats needs fp32 output, no GEGLU, N/ldo/ldr/rowbias_ld %% 4 == 0");
+  }
+  if (a.split_out) {
+    VGEN_REQUIRE(a.split_out == 1 && a.out_dtype != VGEN_F32 && a.epilogue == VGEN_EPI_NONE && a.colstats == nullptr &&
+                     a.N % 32 == 0 && a.ldo % 8 == 0 && a.ldo >= 2 * (int64_t)a.N && (a.residual == nullptr || a.ldr % 4 == 0) &&
+                     (a.rowbias == nullptr || a.rowbias_ld % 4 == 0),
+                 "tapgemm: split_out needs a 16-bit output [M, >= 2 N], no GEGLU / colstats, N %% 32 == 0, ldo %% 8 == 0");
+  }
+  return 0;
+}
+
+extern "C" int vgen_tapgemm_query_plan(const vgen_tapgemm_args* args, int32_t* out3) {
+  if (!plannable(args) || !out3) return VGEN_E_BADARG;
+  const Plan pl = full_plan(*args);
+  out3[0] = pl.shape;
+  out3[1] = pl.bn;
+  out3[2] = pl.splitk;
+  return 0;
+}
+
+extern "C" int vgen_tapgemm_set_plans(const int64_t* rows, int32_t n) {
+  if (n > 0 && !rows) return VGEN_E_BADARG;
+  std::vector<PlanEntry> t;
+  try {
+    t.reserve(n > 0 ? n : 0);
+  } catch (const std::bad_alloc&) {
+    return VGEN_E_BADARG;
+  }
+  for (int i = 0; i < n; ++i) {
+    const int64_t* r = rows + 12 * i;
+    t.push_back(PlanEntry{(int)r[0], r[1], (int)r[2], (int)r[3], (int)r[4], (int)r[5], (int)r[6], (int)r[7], (int)r[8],
+                          (int)r[9], (int)r[10], (int)r[11]});
+  }
+  g_plans.swap(t);
+  g_plans_installed = n >= 0;   // n < 0: back to the compiled-in table
+  return 0;
+}
+
+extern "C" size_t vgen_tapgemm_ws_bytes(const vgen_tapgemm_args* args) {
+  if (!plannable(args)) return 0;
+  const int s = full_plan(*args).splitk;
+  return s > 1 ? (size_t)s * args->M * args->N * sizeof(float) : 0;
+}
