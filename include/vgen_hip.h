@@ -199,6 +199,15 @@ int vgen_tapgemm(const vgen_tapgemm_args* args, void* stream);
  * out_dtype, flags (residual | rowbias<<1 | colstats<<2), shape, bn, splitk}; n < 0 restores the compiled-in table. */
 int vgen_tapgemm_query_plan(const vgen_tapgemm_args* args, int32_t* out3);
 int vgen_tapgemm_set_plans(const int64_t* rows, int32_t n);
+/* The norm planner's answers (csrc/norm_plan.cpp; tests ask these instead of restating the dispatch).  Both validate the
+ * sizes as the launching entry does (VGEN_E_BADARG for a null output or sizes it refuses), launch nothing and need no GPU.
+ * groupnorm: has_cs != 0 asks about vgen_groupnorm_cs -> out4 = {path (0 gn_fused / 1 gn_regs / 2 streaming pipeline /
+ * 3 gn_finalize_cs<256> / 4 gn_finalize_cs<1024>, the last three followed by gn_apply), nsplit (slabs per batch; 0 for the
+ * two single launches), rows per slab, dynamic LDS bytes}.
+ * layernorm: out3 = {lanes per row (16 / 32 / 64), NS (float4 slots per lane of the streaming kernel; 0 = the one-shot
+ * kernel), grid}. */
+int vgen_groupnorm_query_plan(int64_t nb, int64_t S, int32_t C1, int32_t C2, int32_t groups, int32_t has_cs, int32_t* out4);
+int vgen_layernorm_query_plan(int64_t M, int32_t d, int32_t dtype, int32_t* out3);
 
 /* ------------------------------------------------------------------------------------
  * Fused attention, head_dim = 64, softmax(Q K^T * scale) V, no mask / dropout.

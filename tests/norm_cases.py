@@ -356,37 +356,29 @@ def torch_norm(x, nb, S, groups, gamma, beta, eps, silu):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the dispatch of groupnorm_impl (csrc/norms.hip), RESTATED here — keep in step with GNF_* / GNR_* / gn_nsplit there
-GNF_THREADS, GNF_LDS_FLOATS, GNR_THREADS, GNR_NIT, CS_ROWS = 512, 24576, 1024, 36, 64
+# the dispatch of csrc/norm_plan.cpp, ASKED of the library (vgen_groupnorm_query_plan / vgen_layernorm_query_plan launch
+# nothing and need no GPU): nothing of the rule is written down here
+GN_PATHS = ("fused", "regs", "stream", "cs256", "cs1024")        # enum GnPath
+
+
+def _gn_query(nb, S, C1, C2, has_cs):
+    import ctypes
+    from vgen_amd import lib
+    out4 = (ctypes.c_int32 * 4)()
+    lib.check(lib.load().vgen_groupnorm_query_plan(nb, S, C1, C2, GROUPS, int(bool(has_cs)), out4), "vgen_groupnorm_query_plan")
+    return tuple(out4)
 
 
 def gn_path(nb, S, C1, C2, has_cs):
-    C = C1 + C2
-    cpg = C // GROUPS
-    fused_max = (96 if cpg >= 16 else 24) << 20
-    if nb * S * C * 4 <= fused_max and cpg % 2 == 0 and C1 % 2 == 0 and cpg // 2 <= GNF_THREADS and S * cpg <= GNF_LDS_FLOATS:
-        return "fused"
-    I = cpg // 2
-    if (not has_cs and cpg % 2 == 0 and C1 % 2 == 0 and 0 < I <= GNR_THREADS and
-            -(-S // (GNR_THREADS // I)) <= GNR_NIT and nb * GROUPS <= 1024 and S * cpg > GNF_LDS_FLOATS):
-        return "regs"
-    if has_cs:
-        assert S % CS_ROWS == 0
-        return "cs1024" if (S // CS_ROWS) * cpg > 2048 else "cs256"
-    return "stream"
+    return GN_PATHS[_gn_query(nb, S, C1, C2, has_cs)[0]]
 
 
 def gn_nsplit(nb, S, C):
-    """(nsplit, rows per slab, nsplit before the 1024-block floor) of the streaming pipeline (gn_nsplit in norms.hip)."""
-    rows = max(16384 // C, 2)
-    ns0 = -(-S // rows)
-    ns = max(ns0, -(-1024 // nb))
-    ns = max(min(ns, (S + 1) // 2, 1024), 1)
-    return ns, -(-S // ns), ns0
-
-
-def regs_iterations(S, C):
-    return -(-S // (GNR_THREADS // (C // GROUPS // 2)))
+    """(nsplit, rows per slab) of the streaming pipeline, and nsplit before the planner's 1024-block floor: the slabs of ~16 K
+    elements (at least 2 rows) that the shapes of GN_SHAPES["stream"] were chosen around — a property of that choice, not of
+    the dispatch."""
+    _, ns, rows_per, _ = _gn_query(nb, S, C, 0, False)
+    return ns, rows_per, -(-S // max(16384 // C, 2))
 
 
 # (nb, S, C1, C2): the smallest shape per path and edge; ALL families where the tensor is <= 6 M elements, the conditioning
@@ -421,7 +413,12 @@ def gn_variants(path, shape):
 
 # LayerNorm: (M, d, out) with out in {"16", "f32"}; RPB = 256 / LPR rows per block
 def ln_lpr(d):
-    return 16 if d <= 512 else 32 if d <= 1024 else 64
+    """lanes per row of the LayerNorm kernels at width d (the same for both kernels and every output type)"""
+    import ctypes
+    from vgen_amd import lib
+    out3 = (ctypes.c_int32 * 3)()
+    lib.check(lib.load().vgen_layernorm_query_plan(1, d, lib.VGEN_F16, out3), "vgen_layernorm_query_plan")
+    return out3[0]
 
 
 LN_STREAM_WIDTHS = (320, 512, 640, 1024, 1280, 2048)

@@ -87,16 +87,15 @@ def test_a_degenerate_family_is_noticed():
 
 
 def test_case_table_reaches_every_path_and_edge():
-    """gn_path restates groupnorm_impl's dispatch; the table hits every algorithm and the edges between them."""
+    """gn_path asks the library's planner; the table hits every algorithm and the edges between them."""
     for path, shapes in nc.GN_SHAPES.items():
         for nb, S, C1, C2 in shapes:
             assert nc.gn_path(nb, S, C1, C2, path.startswith("cs")) == path, (path, nb, S, C1, C2)
             assert nb * S * (C1 + C2) * 4 <= 72e6
-    cpg = 1280 // 32
-    assert 614 * cpg <= nc.GNF_LDS_FLOATS < 615 * cpg                               # last slice that fits the LDS / first that does not
+    assert (nc.gn_path(2, 614, 1280, 0, False), nc.gn_path(2, 615, 1280, 0, False)) == ("fused", "regs")   # last slice that fits the LDS / first that does not
     assert (2, 33, 640, 320) in nc.GN_SHAPES["fused"] and 640 % (960 // 32) != 0     # group 21 straddles x1 | x2
     assert 128 // 32 == 4                                                            # cpg = 4: one float4 slot per group
-    assert nc.regs_iterations(1836, 1280) == nc.GNR_NIT and nc.regs_iterations(1837, 1280) == nc.GNR_NIT + 1
+    assert (nc.gn_path(2, 1836, 1280, 0, False), nc.gn_path(2, 1837, 1280, 0, False)) == ("regs", "stream")  # last slice that fits the registers / first that does not
     assert any(C2 for _, _, _, C2 in nc.GN_SHAPES["regs"])
     st = nc.GN_SHAPES["stream"]
     assert {-(-(C1 + C2) // 4 // 256) for _, _, C1, C2 in st} == {1, 2, 3}          # float4 slots per thread
@@ -107,7 +106,7 @@ def test_case_table_reaches_every_path_and_edge():
     assert nc.gn_path(4, 13056, 320, 0, False) == "stream"
     items = lambda S, C: (S // 64) * (C // 32)                                      # noqa: E731
     assert items(2496, 320) == 390 and items(3328, 1280) == 2080 > 2048 >= items(640, 1280)
-    assert any(C2 and S % 64 == 0 and S * ((C1 + C2) // 32) > nc.GNF_LDS_FLOATS for _, S, C1, C2 in nc.GN_SHAPES["cs256"])
+    assert any(C2 and S % 64 == 0 and nc.gn_path(nb, S, C1, C2, False) != "fused" for nb, S, C1, C2 in nc.GN_SHAPES["cs256"])   # a slice too big for the LDS
     # after drop_colstats the cs shapes take other paths: all of them held to the same bound
     assert {nc.gn_path(*s, False) for p in ("cs256", "cs1024") for s in nc.GN_SHAPES[p]} == {"regs", "stream"}
     # every path has one shape that takes the raw copies

@@ -18,14 +18,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libvgen_hip.so")
-SOURCES = ["cabi.cpp", "tapgemm_plan.cpp", "tapgemm.hip", "panelgemm.hip", "norms.hip", "attention.hip", "misc.hip", "stems.hip",
-           "adapter.hip", "sketch.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(HERE, "..", "include", "vgen_hip.h")]     # every source's
-# what a source includes beyond HEADERS.  tapgemm_plan.cpp is the tap-GEMM planner: plain C++ (HOST_ONLY: compiled without
-# the HIP language mode, no device pass), so a new plan table (tools/autotune_gemm.py --emit) rebuilds it alone, in seconds
+SOURCES = ["cabi.cpp", "tapgemm_plan.cpp", "norm_plan.cpp", "tapgemm.hip", "panelgemm.hip", "norms.hip", "attention.hip", "misc.hip",
+           "stems.hip", "adapter.hip", "sketch.hip"]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "host_check.h"),
+           os.path.join(HERE, "..", "include", "vgen_hip.h")]                                     # every source's
+# what a source includes beyond HEADERS.  tapgemm_plan.cpp and norm_plan.cpp are the planners: plain C++ (HOST_ONLY: compiled
+# without the HIP language mode, no device pass), so a new plan table (tools/autotune_gemm.py --emit) or a moved norm
+# threshold rebuilds its planner alone, in seconds
 DEPS = {"tapgemm_plan.cpp": ["tapgemm_plan.h", "tapgemm_plans.inc"], "tapgemm.hip": ["tapgemm_plan.h"],
-        "panelgemm.hip": ["tapgemm_plan.h"]}
-HOST_ONLY = {"tapgemm_plan.cpp"}
+        "panelgemm.hip": ["tapgemm_plan.h"], "norm_plan.cpp": ["norm_plan.h"], "norms.hip": ["norm_plan.h"]}
+HOST_ONLY = {"tapgemm_plan.cpp", "norm_plan.cpp"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-inline-asm",
          "-x", "hip"]
 

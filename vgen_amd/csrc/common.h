@@ -190,18 +190,8 @@ template <typename T> struct StoreOf { typedef uint16_t type; };
 template <> struct StoreOf<F32Out> { typedef float type; };
 
 // ---- host-side error plumbing (defined in cabi.cpp) -------------------------------------
-void vgen_set_error(const char* fmt, ...);
+#include "host_check.h"   // vgen_set_error, VGEN_REQUIRE, vgen_aligned16
 int vgen_check_launch(const char* what);
-
-#define VGEN_REQUIRE(cond, ...)       \
-  do {                                \
-    if (!(cond)) {                    \
-      vgen_set_error(__VA_ARGS__);    \
-      return VGEN_E_BADARG;           \
-    }                                 \
-  } while (0)
-
-static inline bool vgen_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
 // Per-DEVICE launch state: hipFuncSetAttribute(MaxDynamicSharedMemorySize) is an attribute of the function ON
 // the current device, and the CU count is the device's — a process that drives several GPUs (the in-process unit

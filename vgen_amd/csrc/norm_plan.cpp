@@ -1,0 +1,127 @@
+// norm_plan.cpp — the norm planner: everything that DECIDES how vgen_groupnorm[_cs] and vgen_layernorm run, nothing that
+// launches.  Host arithmetic only (no HIP header, no device code): it links into a stand-alone program
+// (tests/norm_plan_driver.cpp runs it under the host sanitizers) and an edit here cannot move a kernel instruction.
+// Argument validation of the three entries; which of the five GroupNorm algorithms a shape takes, its split count and the
+// workspace layout; which LayerNorm kernel a width takes, and its grid; the two tuning switches of the GroupNorm dispatch;
+// the two plan queries (tests ask them which path a shape takes instead of restating the rule).
+#include <stdlib.h>
+
+#include "host_check.h"
+#include "norm_plan.h"
+
+namespace {
+
+int env_int(const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
+int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+int gn_nsplit(int64_t nb, int64_t S, int C) {
+  // ~16 K elements (64 KiB of fp32) per block, but at least ~1024 blocks overall when the tensor allows it (>= 2 rows per
+  // block): the 4x7 / 8x14 levels are latency-bound, not bandwidth-bound.
+  int64_t rows = 16384 / C;
+  if (rows < 2) rows = 2;
+  int64_t ns = ceil_div(S, rows);
+  const int64_t want = ceil_div(1024, nb);
+  if (ns < want) ns = want;
+  const int64_t cap = (S + 1) / 2;
+  if (ns > cap) ns = cap;
+  if (ns < 1) ns = 1;
+  if (ns > GN_MAX_NSPLIT) ns = GN_MAX_NSPLIT;
+  return (int)ns;
+}
+
+}  // namespace
+
+extern "C" size_t vgen_groupnorm_ws_bytes(int64_t nb, int64_t S) {
+  // partials at the upper bound of nsplit (independent of C so callers need not pass it) + per-channel (scale, shift)
+  return (size_t)(nb * GN_MAX_NSPLIT * GN_G * 3 + nb * GN_MAX_C * 2) * sizeof(float);
+}
+
+int gn_validate(const GnArgs& a) {
+  const int C = a.C1 + a.C2;
+  if (a.want_cs) {
+    VGEN_REQUIRE(a.cs1 != nullptr && (a.C2 == 0 || a.cs2 != nullptr), "groupnorm_cs: missing column statistics");
+    VGEN_REQUIRE(a.S % GN_CS_ROWS == 0, "groupnorm_cs: S=%lld must be a multiple of the 64-row slab", (long long)a.S);
+  }
+  VGEN_REQUIRE(a.dtype == VGEN_BF16 || a.dtype == VGEN_F16, "groupnorm: dtype");
+  VGEN_REQUIRE(a.groups > 0 && a.groups <= GN_G && C % a.groups == 0, "groupnorm: C=%d groups=%d", C, a.groups);
+  VGEN_REQUIRE(a.C1 > 0 && a.C1 % 4 == 0 && a.C2 >= 0 && a.C2 % 4 == 0 && C <= GN_MAX_C,
+               "groupnorm: C1=%d C2=%d (need %%4, total <= 3072)", a.C1, a.C2);
+  VGEN_REQUIRE(a.C2 == 0 || a.x2 != nullptr, "groupnorm: x2 null with C2 > 0");
+  VGEN_REQUIRE(vgen_aligned16(a.x1) && vgen_aligned16(a.x2) && vgen_aligned16(a.y) && vgen_aligned16(a.raw) && vgen_aligned16(a.ws),
+               "groupnorm: alignment");
+  VGEN_REQUIRE(a.nb > 0 && a.S > 0 && a.nb <= 65535, "groupnorm: nb=%lld S=%lld", (long long)a.nb, (long long)a.S);
+  if (a.ws_bytes < vgen_groupnorm_ws_bytes(a.nb, a.S)) {
+    vgen_set_error("groupnorm: workspace %zu < %zu", a.ws_bytes, vgen_groupnorm_ws_bytes(a.nb, a.S));
+    return VGEN_E_WORKSPACE;
+  }
+  // rpb * C must fit the LDS staging of gn_stats (GN_MAX_C floats per plane): holds for every C admitted above
+  const int nslots = C / 4;
+  const int rpb = nslots <= GN_THREADS ? GN_THREADS / nslots : 1;
+  VGEN_REQUIRE(rpb * C <= GN_MAX_C, "groupnorm: internal LDS bound");
+  return 0;
+}
+
+GnPlan gn_plan(int64_t nb, int64_t S, int C1, int C2, int groups, bool has_cs) {
+  const int C = C1 + C2;
+  const int cpg = C / groups;
+  const int I = cpg / 2;                                  // float2 items per row of a group
+  const bool pairs = cpg % 2 == 0 && C1 % 2 == 0;        // both single-launch kernels walk a slice in channel pairs
+  // tuning switch (not part of the ABI): VGEN_GN_FUSED_MAX_MB (0 keeps everything on the streaming pipeline).  A slice row
+  // is only cpg * 4 bytes: at C = 320 (40 B) every 128-byte line is fetched by 3-4 blocks and big tensors lose (76 vs 53 us
+  // on [32 x 1792 x 320]); from 80-byte rows on the single launch wins as long as the slice fits the LDS (24 vs 40 us on
+  // [32 x 448 x 640]).
+  static const int env_max = env_int("VGEN_GN_FUSED_MAX_MB", -1);
+  const int64_t fused_max = (int64_t)(env_max >= 0 ? env_max : (cpg >= 16 ? 96 : 24)) << 20;
+  if (nb * S * C * 4 <= fused_max && pairs && I <= GNF_THREADS && S * cpg <= GNF_LDS_FLOATS)
+    return GnPlan{GN_FUSED, 0, (size_t)S * cpg * sizeof(float), 0};
+  // register-resident single launch: slices that missed the LDS path but fit 72 floats x 1024 threads and are few
+  // enough that one block per slice is not the bottleneck (tuning switch: VGEN_GN_REGS=0 disables)
+  static const int regs_on = env_int("VGEN_GN_REGS", 1);
+  if (regs_on && !has_cs && pairs && I > 0 && I <= GNR_THREADS && ceil_div(S, GNR_THREADS / I) <= GNR_NIT &&
+      nb * groups <= GNR_MAX_BLOCKS && S * cpg > GNF_LDS_FLOATS)
+    return GnPlan{GN_REGS, 0, 0, 0};
+  const int ns = gn_nsplit(nb, S, C);
+  const int path = !has_cs ? GN_STREAM : (S / GN_CS_ROWS) * cpg > GN_CS_ITEMS_256 ? GN_CS1024 : GN_CS256;
+  return GnPlan{path, ns, 0, nb * ns * GN_G * 3};
+}
+
+int ln_validate(const void* x, int64_t M, int32_t d, const void* gamma, const void* beta, const void* y, int32_t dtype) {
+  VGEN_REQUIRE(dtype == VGEN_BF16 || dtype == VGEN_F16 || dtype == VGEN_F32, "layernorm: dtype");
+  VGEN_REQUIRE(d > 0 && d % 4 == 0 && d <= LN_MAX_D, "layernorm: d=%d", d);
+  VGEN_REQUIRE(vgen_aligned16(x) && vgen_aligned16(y) && vgen_aligned16(gamma) && vgen_aligned16(beta), "layernorm: alignment");
+  VGEN_REQUIRE(M < (1LL << 32), "layernorm: M too large");   // M <= 0 is a no-op of the entry, not an error
+  return 0;
+}
+
+LnPlan ln_plan(int64_t M, int d, int dtype) {
+  LnPlan p{d <= 512 ? 16 : d <= 1024 ? 32 : 64, 0, 0};
+  if (dtype != VGEN_F32)
+    for (const LnWidth& w : LN_STREAM)
+      if (w.d == d) p = LnPlan{w.lpr, w.ns, 0};
+  const int64_t row_groups = ceil_div(M, LN_THREADS / p.lpr);
+  p.grid = (unsigned)(p.ns && row_groups > LN_STREAM_GRID ? LN_STREAM_GRID : row_groups);
+  return p;
+}
+
+// ---- plan queries: validate with stand-in operands, plan, launch nothing ------------------------------------------------
+extern "C" int vgen_groupnorm_query_plan(int64_t nb, int64_t S, int32_t C1, int32_t C2, int32_t groups, int32_t has_cs,
+                                         int32_t* out4) {
+  alignas(16) static const char operand[16] = {0};   // aligned and non-null: nothing here dereferences an operand
+  if (!out4) return VGEN_E_BADARG;
+  GnArgs a{};
+  a.x1 = a.y = a.ws = operand, a.x2 = C2 ? operand : nullptr;
+  a.cs1 = has_cs ? operand : nullptr, a.cs2 = has_cs && C2 ? operand : nullptr;
+  a.C1 = C1, a.C2 = C2, a.groups = groups, a.dtype = VGEN_F16, a.nb = nb, a.S = S, a.ws_bytes = (size_t)-1;
+  a.want_cs = has_cs != 0;
+  if (gn_validate(a) != 0) return VGEN_E_BADARG;
+  const GnPlan p = gn_plan(nb, S, C1, C2, groups, a.want_cs);
+  out4[0] = p.path, out4[1] = p.nsplit, out4[2] = p.nsplit ? (int32_t)ceil_div(S, p.nsplit) : 0, out4[3] = (int32_t)p.lds_bytes;
+  return 0;
+}
+
+extern "C" int vgen_layernorm_query_plan(int64_t M, int32_t d, int32_t dtype, int32_t* out3) {
+  if (!out3 || ln_validate(nullptr, M, d, nullptr, nullptr, nullptr, dtype) != 0) return VGEN_E_BADARG;
+  const LnPlan p = ln_plan(M > 0 ? M : 0, d, dtype);
+  out3[0] = p.lpr, out3[1] = p.ns, out3[2] = (int32_t)p.grid;
+  return 0;
+}

@@ -11,15 +11,14 @@
 //                   registers; 8-byte 16-bit stores.
 // The reduction order is fixed (no atomics) so results are run-to-run deterministic.
 // The input row is the virtual concat [x1 | x2] (decoder skip connections).
+// Small tensors take one of two single launches (gn_fused, gn_regs); gn_finalize_cs replaces 1 and 2 where the producing
+// tap-GEMM wrote column statistics.  This file holds the kernels and launches them: WHICH of them a shape takes, the
+// constants they are sized by, the workspace layout and every argument check are norm_plan.{h,cpp} (host-only).
 #include "common.h"
-#include <stdlib.h>
+#include "norm_plan.h"
 #include <type_traits>
 
 namespace {
-
-constexpr int GN_THREADS = 256;
-constexpr int GN_MAX_SLOTS = 3;   // float4 slots per thread -> C <= 3072
-constexpr int GN_G = 32;          // groups supported per launch (reference always uses 32)
 
 struct GnGeom {
   int C, C1, C2;
@@ -68,7 +67,7 @@ __device__ __forceinline__ f32x4 gn_load(const float* x1, const float* x2, const
 __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(
     const float* __restrict__ x1, int C1, const float* __restrict__ x2, int C2, int64_t S,
     int groups, int nsplit, float* __restrict__ part) {
-  __shared__ float red[2][3072];  // [mean|M2][rowlane * C + c]  (rpb * C <= 1024 when rpb > 1)
+  __shared__ float red[2][GN_MAX_C];  // [mean|M2][rowlane * C + c]  (rpb * C <= 1024 when rpb > 1)
   const GnGeom g = gn_geom(C1, C2, groups);
   const int tid = threadIdx.x;
   const int split = blockIdx.x;
@@ -249,7 +248,7 @@ __global__ __launch_bounds__(NT) void gn_finalize_cs_kernel(const float* __restr
   const int grp = blockIdx.x;
   const int64_t nb = blockIdx.y;
   const int cpg = (C1 + C2) / groups;
-  const int slabs = (int)(S / 64);
+  const int slabs = (int)(S / GN_CS_ROWS);
   const int items = slabs * cpg;
   const int64_t srow0 = nb * slabs;
   float n = 0.f, mean = 0.f, m2 = 0.f;
@@ -474,10 +473,11 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(
 // Larger slices stay on the streaming pipeline: a single block per slice is latency-bound (one CU
 // pulls ~20 GB/s with 16 KiB in flight; measured 51 us vs 26 us on [2 x 1792 x 1280]).
 // Fixed reduction order: wave butterflies, then the wave partials in index order.
-constexpr int GNF_THREADS = 512;         // r04 same-box A/B of the whole step: 256 threads +0.3 %, 1024 +0.35 % (profiles/r04f_ab_gnf_threads.jsonl)
-constexpr int GNF_LDS_FLOATS = 24576;   // 96 KiB of the CU's 160 KiB
+// (GNF_THREADS = 512 threads, GNF_LDS_FLOATS = 96 KiB of the CU's 160 KiB: norm_plan.h)
 
-__device__ __forceinline__ float gnf_block_sum(float v, float* red) {
+// sum over a block of NT threads, in every thread: wave butterflies, then the NT / 64 wave partials in index order
+template <int NT>
+__device__ __forceinline__ float block_sum(float v, float* red) {
   v = wave_sum(v);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   __syncthreads();                       // red[] may still be read from the previous reduction
@@ -485,7 +485,7 @@ __device__ __forceinline__ float gnf_block_sum(float v, float* red) {
   __syncthreads();
   float t = 0.f;
 #pragma unroll
-  for (int i = 0; i < GNF_THREADS / 64; ++i) t += red[i];
+  for (int i = 0; i < NT / 64; ++i) t += red[i];
   return t;
 }
 
@@ -525,14 +525,14 @@ __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(
     }
   }
   const float n = (float)S * (float)cpg;
-  const float mean = gnf_block_sum(a, red) / n;
+  const float mean = block_sum<GNF_THREADS>(a, red) / n;
   float q = 0.f;
   for (int k = 0; k < nit; ++k) {
     const f32x2 v = st[k * sstep];
     const float d0 = v.x - mean, d1 = v.y - mean;
     q += d0 * d0 + d1 * d1;
   }
-  const float rstd = 1.0f / sqrtf(gnf_block_sum(q, red) / n + eps);
+  const float rstd = 1.0f / sqrtf(block_sum<GNF_THREADS>(q, red) / n + eps);
   if (!active) return;
   const float sc0 = gamma[c] * rstd, sc1 = gamma[c + 1] * rstd;
   const float sh0 = beta[c] - mean * sc0, sh1 = beta[c + 1] - mean * sc1;
@@ -559,21 +559,7 @@ __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(
 // dependent launches that each re-read it.  A 1024-thread block can hold such a slice in its registers (72 floats
 // per thread): load once (the loads ARE the staging), block-reduce the mean, centred variance from the registers,
 // normalise + SiLU + store.  One launch, 6 B / element instead of 10.  Fixed reduction order.
-constexpr int GNR_THREADS = 1024;
-constexpr int GNR_NIT = 36;                       // float2 items per thread
-
-__device__ __forceinline__ float gnr_block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < GNR_THREADS / 64; ++i) t += red[i];
-  return t;
-}
-
+// (GNR_THREADS = 1024 threads x GNR_NIT = 36 float2 items: norm_plan.h)
 template <typename T>
 __global__ __launch_bounds__(GNR_THREADS) void gn_regs_kernel(
     const float* __restrict__ x1, int C1, const float* __restrict__ x2, int C2, int64_t S, int groups,
@@ -609,7 +595,7 @@ __global__ __launch_bounds__(GNR_THREADS) void gn_regs_kernel(
     for (int k = 0; k < GNR_NIT; ++k) a += v[k].x + v[k].y;      // rows beyond nit hold zeros
   }
   const float n = (float)S * (float)cpg;
-  const float mean = gnr_block_sum(a, red) / n;
+  const float mean = block_sum<GNR_THREADS>(a, red) / n;
   float q = 0.f;
 #pragma unroll
   for (int k = 0; k < GNR_NIT; ++k) {
@@ -618,7 +604,7 @@ __global__ __launch_bounds__(GNR_THREADS) void gn_regs_kernel(
       q += d0 * d0 + d1 * d1;
     }
   }
-  const float rstd = 1.0f / sqrtf(gnr_block_sum(q, red) / n + eps);
+  const float rstd = 1.0f / sqrtf(block_sum<GNR_THREADS>(q, red) / n + eps);
   if (!active) return;
   const float sc0 = gamma[c] * rstd, sc1 = gamma[c + 1] * rstd;
   const float sh0 = beta[c] - mean * sc0, sh1 = beta[c + 1] - mean * sc1;
@@ -640,33 +626,17 @@ __global__ __launch_bounds__(GNR_THREADS) void gn_regs_kernel(
   }
 }
 
-int gn_nsplit(int64_t nb, int64_t S, int C) {
-  // ~16 K elements (64 KiB of fp32) per block, but at least ~1024 blocks overall when the tensor
-  // allows it (>= 2 rows per block): the 4x7 / 8x14 levels are latency-bound, not bandwidth-bound.
-  int64_t rows = 16384 / C;
-  if (rows < 2) rows = 2;
-  int64_t ns = (S + rows - 1) / rows;
-  const int64_t want = (1024 + nb - 1) / nb;
-  if (ns < want) ns = want;
-  const int64_t cap = (S + 1) / 2;
-  if (ns > cap) ns = cap;
-  if (ns < 1) ns = 1;
-  if (ns > 1024) ns = 1024;
-  return (int)ns;
-}
-
 // ---- LayerNorm: LPR lanes per row (16 / 32 / 64), two-pass from registers ------------------
 // d = 320..1280 in the UNet: one 64-lane wave per 1.25 KiB row left most lanes idle and one load in
 // flight per wave (1.2 TB/s measured); with 16 lanes per row a wave streams 4 rows at once.
-constexpr int LN_MAX_SLOTS = 8;  // float4 slots per lane: d <= 4 * 8 * LPR
-
+// (LN_MAX_SLOTS = 8 float4 slots per lane: d <= 4 * 8 * LPR)
 template <typename T, int LPR>
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t M,
+__global__ __launch_bounds__(LN_THREADS) void layernorm_kernel(const float* __restrict__ x, int64_t M,
                                                         int d, float eps,
                                                         const float* __restrict__ gamma,
                                                         const float* __restrict__ beta,
                                                         void* __restrict__ y) {
-  constexpr int RPB = 256 / LPR;  // rows per block
+  constexpr int RPB = LN_THREADS / LPR;  // rows per block
   const int sub = threadIdx.x % LPR;
   const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
   const bool live = row < M;
@@ -721,11 +691,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 // and stored — and gamma / beta live in registers.  The one-shot kernel above launches one short
 // wave per 4 rows (14 K waves at M = 57344): 2.85 TB/s; wave turnover, not bandwidth, was the bound.
 template <typename T, int LPR, int NS>
-__global__ __launch_bounds__(256) void layernorm_stream_kernel(const float* __restrict__ x, int64_t M,
+__global__ __launch_bounds__(LN_THREADS) void layernorm_stream_kernel(const float* __restrict__ x, int64_t M,
                                                                float eps, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta,
                                                                uint16_t* __restrict__ y) {
-  constexpr int RPB = 256 / LPR;
+  constexpr int RPB = LN_THREADS / LPR;
   constexpr int D = NS * 4 * LPR;
   const int sub = threadIdx.x % LPR;
   const int rl = threadIdx.x / LPR;
@@ -775,190 +745,114 @@ __global__ __launch_bounds__(256) void layernorm_stream_kernel(const float* __re
   }
 }
 
+// ---- launches: norm_plan.cpp decides, this launches what it answers ------------------------------------------------------
+// NS = 0: the one-shot kernel
 template <typename T, int LPR, int NS>
-void launch_ln_stream(const float* x, int64_t M, float eps, const float* gamma, const float* beta,
-                      uint16_t* y, hipStream_t s) {
-  const int64_t ngroups = (M + 256 / LPR - 1) / (256 / LPR);
-  const int64_t grid = ngroups < 2048 ? ngroups : 2048;     // 8 blocks per CU
-  hipLaunchKernelGGL((layernorm_stream_kernel<T, LPR, NS>), dim3((unsigned)grid), dim3(256), 0, s, x, M, eps,
-                     gamma, beta, y);
-}
-
-template <typename T, int LPR>
-void launch_ln(const float* x, int64_t M, int d, float eps, const float* gamma, const float* beta,
-               void* y, hipStream_t s) {
-  const int64_t grid = (M + 256 / LPR - 1) / (256 / LPR);
-  hipLaunchKernelGGL((layernorm_kernel<T, LPR>), dim3((unsigned)grid), dim3(256), 0, s, x, M, d, eps,
-                     gamma, beta, y);
-}
-
-template <typename T>
-void dispatch_ln(const float* x, int64_t M, int d, float eps, const float* gamma, const float* beta,
-                 uint16_t* y, hipStream_t s) {
-  switch (d) {   // exact-width streaming kernels
-    case 320: return launch_ln_stream<T, 16, 5>(x, M, eps, gamma, beta, y, s);
-    case 512: return launch_ln_stream<T, 16, 8>(x, M, eps, gamma, beta, y, s);
-    case 640: return launch_ln_stream<T, 32, 5>(x, M, eps, gamma, beta, y, s);
-    case 1024: return launch_ln_stream<T, 32, 8>(x, M, eps, gamma, beta, y, s);
-    case 1280: return launch_ln_stream<T, 64, 5>(x, M, eps, gamma, beta, y, s);
-    case 2048: return launch_ln_stream<T, 64, 8>(x, M, eps, gamma, beta, y, s);
-    default: break;
+void ln_launch(const float* x, int64_t M, int d, float eps, const float* gamma, const float* beta, void* y, unsigned grid,
+               hipStream_t s) {
+  if constexpr (NS == 0) {
+    hipLaunchKernelGGL((layernorm_kernel<T, LPR>), dim3(grid), dim3(LN_THREADS), 0, s, x, M, d, eps, gamma, beta, y);
+  } else {
+    hipLaunchKernelGGL((layernorm_stream_kernel<T, LPR, NS>), dim3(grid), dim3(LN_THREADS), 0, s, x, M, eps, gamma, beta,
+                       (uint16_t*)y);
   }
-  if (d <= 512) launch_ln<T, 16>(x, M, d, eps, gamma, beta, y, s);
-  else if (d <= 1024) launch_ln<T, 32>(x, M, d, eps, gamma, beta, y, s);
-  else launch_ln<T, 64>(x, M, d, eps, gamma, beta, y, s);
 }
 
-}  // namespace
+// every LayerNorm kernel there is: [dtype][LPR 16 | 32 | 64][NS 0 | 5 | 8] (LN_STREAM; fp32 output: the one-shot kernel only)
+typedef void (*LnLaunch)(const float*, int64_t, int, float, const float*, const float*, void*, unsigned, hipStream_t);
+#define LN_ROW(T, LPR) {ln_launch<T, LPR, 0>, ln_launch<T, LPR, 5>, ln_launch<T, LPR, 8>}
+constexpr LnLaunch kLnLaunch[3][3][3] = {
+    {LN_ROW(BF16, 16), LN_ROW(BF16, 32), LN_ROW(BF16, 64)},
+    {LN_ROW(F16, 16), LN_ROW(F16, 32), LN_ROW(F16, 64)},
+    {{ln_launch<F32Out, 16, 0>}, {ln_launch<F32Out, 32, 0>}, {ln_launch<F32Out, 64, 0>}}};
+#undef LN_ROW
+static_assert(VGEN_BF16 == 0 && VGEN_F16 == 1 && VGEN_F32 == 2, "kLnLaunch is indexed by the dtype enum");
 
-extern "C" size_t vgen_groupnorm_ws_bytes(int64_t nb, int64_t S) {
-  const int ns = 1024;   // upper bound of gn_nsplit (independent of C so callers need not pass it)
-  return (size_t)(nb * ns * GN_G * 3 + nb * 3072 * 2) * sizeof(float);   // partials + per-channel (scale, shift)
+// f(BF16{}) or f(F16{}): the one place where a launch's 16-bit storage type is chosen
+template <typename F>
+int with_storage(int dtype, F&& f) {
+  return dtype == VGEN_BF16 ? f(BF16{}) : f(F16{});
 }
 
-static int groupnorm_impl(const float* x1, int32_t C1, const float* cs1, const float* x2, int32_t C2,
-                          const float* cs2, int64_t nb, int64_t S, int32_t groups, float eps,
-                          const float* gamma, const float* beta, int32_t silu, void* y,
-                          void* raw, int32_t raw_split, int32_t dtype, float* ws, size_t ws_bytes,
-                          void* stream) {
-  const int C = C1 + C2;
-  const int raw_lo = (raw != nullptr && raw_split) ? C : 0;
-  VGEN_REQUIRE(dtype == VGEN_BF16 || dtype == VGEN_F16, "groupnorm: dtype");
-  VGEN_REQUIRE(groups > 0 && groups <= GN_G && C % groups == 0, "groupnorm: C=%d groups=%d", C,
-               groups);
-  VGEN_REQUIRE(C1 > 0 && C1 % 4 == 0 && C2 >= 0 && C2 % 4 == 0 && C <= 3072,
-               "groupnorm: C1=%d C2=%d (need %%4, total <= 3072)", C1, C2);
-  VGEN_REQUIRE(C2 == 0 || x2 != nullptr, "groupnorm: x2 null with C2 > 0");
-  VGEN_REQUIRE(vgen_aligned16(x1) && vgen_aligned16(x2) && vgen_aligned16(y) &&
-                   vgen_aligned16(raw) && vgen_aligned16(ws),
-               "groupnorm: alignment");
-  VGEN_REQUIRE(nb > 0 && S > 0 && nb <= 65535, "groupnorm: nb=%lld S=%lld", (long long)nb,
-               (long long)S);
-  if (ws_bytes < vgen_groupnorm_ws_bytes(nb, S)) {
-    vgen_set_error("groupnorm: workspace %zu < %zu", ws_bytes, vgen_groupnorm_ws_bytes(nb, S));
-    return VGEN_E_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  {
-    // tuning switch (not part of the ABI): VGEN_GN_FUSED_MAX_MB (0 keeps everything on the streaming
-    // pipeline).  A slice row is only cpg * 4 bytes: at C = 320 (40 B) every 128-byte line is fetched by
-    // 3-4 blocks and big tensors lose (76 vs 53 us on [32 x 1792 x 320]); from 80-byte rows on the
-    // single launch wins as long as the slice fits the LDS (24 vs 40 us on [32 x 448 x 640]).
-    static const int env_max = getenv("VGEN_GN_FUSED_MAX_MB") ? atoi(getenv("VGEN_GN_FUSED_MAX_MB")) : -1;
-    const int64_t fused_max = (int64_t)(env_max >= 0 ? env_max : (C / groups >= 16 ? 96 : 24)) << 20;
-    const int cpg = C / groups;
-    if (nb * S * C * 4 <= fused_max && cpg % 2 == 0 && C1 % 2 == 0 && cpg / 2 <= GNF_THREADS && S * cpg <= GNF_LDS_FLOATS) {
-      const size_t lds = (size_t)S * cpg * sizeof(float);
+int groupnorm_impl(const float* x1, int32_t C1, const float* cs1, const float* x2, int32_t C2, const float* cs2, int64_t nb,
+                   int64_t S, int32_t groups, float eps, const float* gamma, const float* beta, int32_t silu, void* y,
+                   void* raw, int32_t raw_split, int32_t dtype, float* ws, size_t ws_bytes, void* stream, bool want_cs) {
+  int rc = gn_validate(GnArgs{x1, cs1, x2, cs2, y, raw, ws, C1, C2, groups, dtype, nb, S, ws_bytes, want_cs});
+  if (rc) return rc;
+  const GnPlan plan = gn_plan(nb, S, C1, C2, groups, cs1 != nullptr);
+  const int C = C1 + C2, raw_lo = (raw != nullptr && raw_split) ? C : 0;
+  uint16_t *const y16 = (uint16_t*)y, *const raw16 = (uint16_t*)raw;
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 slices((unsigned)groups, (unsigned)nb);         // one block per (batch, group)
+  const dim3 slabs((unsigned)plan.nsplit, (unsigned)nb);     // one block per slab of rows
+  float *const part = ws, *const stat = ws + plan.part_floats;
+  switch (plan.path) {
+    case GN_FUSED: {
       static bool done_bf16[VGEN_MAX_DEVICES] = {false}, done_f16[VGEN_MAX_DEVICES] = {false};
       if (vgen_lds_optin((const void*)gn_fused_kernel<BF16>, GNF_LDS_FLOATS * 4, done_bf16, "groupnorm") ||
           vgen_lds_optin((const void*)gn_fused_kernel<F16>, GNF_LDS_FLOATS * 4, done_f16, "groupnorm"))
         return VGEN_E_BADARG;
-      dim3 fgrid((unsigned)groups, (unsigned)nb);
-      if (dtype == VGEN_BF16) {
-        hipLaunchKernelGGL(gn_fused_kernel<BF16>, fgrid, dim3(GNF_THREADS), lds, s, x1, C1, x2, C2, S, groups, eps,
-                           gamma, beta, silu, (uint16_t*)y, (uint16_t*)raw, raw_lo);
-      } else {
-        hipLaunchKernelGGL(gn_fused_kernel<F16>, fgrid, dim3(GNF_THREADS), lds, s, x1, C1, x2, C2, S, groups, eps,
-                           gamma, beta, silu, (uint16_t*)y, (uint16_t*)raw, raw_lo);
-      }
-      return vgen_check_launch("gn_fused");
+      return with_storage(dtype, [&](auto t) {
+        hipLaunchKernelGGL(gn_fused_kernel<decltype(t)>, slices, dim3(GNF_THREADS), plan.lds_bytes, s, x1, C1, x2, C2, S,
+                           groups, eps, gamma, beta, silu, y16, raw16, raw_lo);
+        return vgen_check_launch("gn_fused");
+      });
     }
+    case GN_REGS:
+      return with_storage(dtype, [&](auto t) {
+        hipLaunchKernelGGL(gn_regs_kernel<decltype(t)>, slices, dim3(GNR_THREADS), 0, s, x1, C1, x2, C2, S, groups, eps,
+                           gamma, beta, silu, y16, raw16, raw_lo);
+        return vgen_check_launch("gn_regs");
+      });
+    case GN_CS1024:
+      hipLaunchKernelGGL(gn_finalize_cs_kernel<1024>, slices, dim3(1024), 0, s, cs1, C1, cs2, C2, x1, x2, S, groups, eps,
+                         gamma, beta, stat);
+      rc = vgen_check_launch("gn_finalize_cs");
+      break;
+    case GN_CS256:
+      hipLaunchKernelGGL(gn_finalize_cs_kernel<256>, slices, dim3(256), 0, s, cs1, C1, cs2, C2, x1, x2, S, groups, eps,
+                         gamma, beta, stat);
+      rc = vgen_check_launch("gn_finalize_cs");
+      break;
+    default:   // GN_STREAM
+      hipLaunchKernelGGL(gn_stats_kernel, slabs, dim3(GN_THREADS), 0, s, x1, C1, x2, C2, S, groups, plan.nsplit, part);
+      rc = vgen_check_launch("gn_stats");
+      if (rc) return rc;
+      hipLaunchKernelGGL(gn_finalize_kernel, slices, dim3(64), 0, s, part, groups, plan.nsplit, eps, C, gamma, beta, stat);
+      rc = vgen_check_launch("gn_finalize");
+      break;
   }
-  {
-    // register-resident single launch: slices that missed the LDS path but fit 72 floats x 1024 threads and are few
-    // enough that one block per slice is not the bottleneck (tuning switch: VGEN_GN_REGS=0 disables)
-    static const int regs_on = getenv("VGEN_GN_REGS") ? atoi(getenv("VGEN_GN_REGS")) : 1;
-    const int cpg = C / groups;
-    const int I = cpg / 2;
-    if (regs_on && cs1 == nullptr && cpg % 2 == 0 && C1 % 2 == 0 && I > 0 && I <= GNR_THREADS &&
-        (S + (GNR_THREADS / I) - 1) / (GNR_THREADS / I) <= GNR_NIT && nb * groups <= 1024 && S * cpg > GNF_LDS_FLOATS) {
-      dim3 fgrid((unsigned)groups, (unsigned)nb);
-      if (dtype == VGEN_BF16) {
-        hipLaunchKernelGGL(gn_regs_kernel<BF16>, fgrid, dim3(GNR_THREADS), 0, s, x1, C1, x2, C2, S, groups, eps, gamma, beta,
-                           silu, (uint16_t*)y, (uint16_t*)raw, raw_lo);
-      } else {
-        hipLaunchKernelGGL(gn_regs_kernel<F16>, fgrid, dim3(GNR_THREADS), 0, s, x1, C1, x2, C2, S, groups, eps, gamma, beta,
-                           silu, (uint16_t*)y, (uint16_t*)raw, raw_lo);
-      }
-      return vgen_check_launch("gn_regs");
-    }
-  }
-  // rpb * C must fit the LDS staging of gn_stats (3072 floats per plane)
-  const int nslots = C / 4;
-  const int rpb = nslots <= GN_THREADS ? GN_THREADS / nslots : 1;
-  VGEN_REQUIRE(rpb * C <= 3072, "groupnorm: internal LDS bound");
-  const int ns = gn_nsplit(nb, S, C);
-  float* part = ws;
-  float* stat = ws + nb * ns * GN_G * 3;
-  dim3 grid((unsigned)ns, (unsigned)nb);
-  int rc;
-  if (cs1 != nullptr) {
-    if ((S / 64) * (C / groups) > 2048) {
-      hipLaunchKernelGGL(gn_finalize_cs_kernel<1024>, dim3((unsigned)groups, (unsigned)nb), dim3(1024), 0, s, cs1, C1,
-                         cs2, C2, x1, x2, S, groups, eps, gamma, beta, stat);
-    } else {
-      hipLaunchKernelGGL(gn_finalize_cs_kernel<256>, dim3((unsigned)groups, (unsigned)nb), dim3(256), 0, s, cs1, C1,
-                         cs2, C2, x1, x2, S, groups, eps, gamma, beta, stat);
-    }
-    rc = vgen_check_launch("gn_finalize_cs");
-    if (rc) return rc;
-  } else {
-    hipLaunchKernelGGL(gn_stats_kernel, grid, dim3(GN_THREADS), 0, s, x1, C1, x2, C2, S, groups, ns,
-                       part);
-    rc = vgen_check_launch("gn_stats");
-    if (rc) return rc;
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)groups, (unsigned)nb), dim3(64), 0, s, part,
-                       groups, ns, eps, C, gamma, beta, stat);
-    rc = vgen_check_launch("gn_finalize");
-    if (rc) return rc;
-  }
-  if (dtype == VGEN_BF16) {
-    hipLaunchKernelGGL(gn_apply_kernel<BF16>, grid, dim3(GN_THREADS), 0, s, x1, C1, x2, C2, S,
-                       groups, ns, stat, gamma, beta, silu, (uint16_t*)y, (uint16_t*)raw, raw_lo);
-  } else {
-    hipLaunchKernelGGL(gn_apply_kernel<F16>, grid, dim3(GN_THREADS), 0, s, x1, C1, x2, C2, S,
-                       groups, ns, stat, gamma, beta, silu, (uint16_t*)y, (uint16_t*)raw, raw_lo);
-  }
-  return vgen_check_launch("gn_apply");
+  if (rc) return rc;
+  return with_storage(dtype, [&](auto t) {
+    hipLaunchKernelGGL(gn_apply_kernel<decltype(t)>, slabs, dim3(GN_THREADS), 0, s, x1, C1, x2, C2, S, groups, plan.nsplit,
+                       stat, gamma, beta, silu, y16, raw16, raw_lo);
+    return vgen_check_launch("gn_apply");
+  });
 }
 
-extern "C" int vgen_groupnorm(const float* x1, int32_t C1, const float* x2, int32_t C2,
-                              int64_t nb, int64_t S, int32_t groups, float eps,
-                              const float* gamma, const float* beta, int32_t silu, void* y,
-                              void* raw, int32_t raw_split, int32_t dtype, float* ws, size_t ws_bytes,
-                              void* stream) {
-  return groupnorm_impl(x1, C1, nullptr, x2, C2, nullptr, nb, S, groups, eps, gamma, beta, silu, y, raw, raw_split,
-                        dtype, ws, ws_bytes, stream);
+}  // namespace
+
+extern "C" int vgen_groupnorm(const float* x1, int32_t C1, const float* x2, int32_t C2, int64_t nb, int64_t S, int32_t groups,
+                              float eps, const float* gamma, const float* beta, int32_t silu, void* y, void* raw,
+                              int32_t raw_split, int32_t dtype, float* ws, size_t ws_bytes, void* stream) {
+  return groupnorm_impl(x1, C1, nullptr, x2, C2, nullptr, nb, S, groups, eps, gamma, beta, silu, y, raw, raw_split, dtype, ws,
+                        ws_bytes, stream, false);
 }
 
-extern "C" int vgen_groupnorm_cs(const float* x1, int32_t C1, const float* cs1, const float* x2,
-                                 int32_t C2, const float* cs2, int64_t nb, int64_t S, int32_t groups,
-                                 float eps, const float* gamma, const float* beta, int32_t silu,
-                                 void* y, void* raw, int32_t raw_split, int32_t dtype, float* ws, size_t ws_bytes,
-                                 void* stream) {
-  VGEN_REQUIRE(cs1 != nullptr && (C2 == 0 || cs2 != nullptr), "groupnorm_cs: missing column statistics");
-  VGEN_REQUIRE(S % 64 == 0, "groupnorm_cs: S=%lld must be a multiple of the 64-row slab", (long long)S);
-  return groupnorm_impl(x1, C1, cs1, x2, C2, cs2, nb, S, groups, eps, gamma, beta, silu, y, raw, raw_split, dtype,
-                        ws, ws_bytes, stream);
+extern "C" int vgen_groupnorm_cs(const float* x1, int32_t C1, const float* cs1, const float* x2, int32_t C2, const float* cs2,
+                                 int64_t nb, int64_t S, int32_t groups, float eps, const float* gamma, const float* beta,
+                                 int32_t silu, void* y, void* raw, int32_t raw_split, int32_t dtype, float* ws,
+                                 size_t ws_bytes, void* stream) {
+  return groupnorm_impl(x1, C1, cs1, x2, C2, cs2, nb, S, groups, eps, gamma, beta, silu, y, raw, raw_split, dtype, ws, ws_bytes,
+                        stream, true);
 }
 
-extern "C" int vgen_layernorm(const float* x, int64_t M, int32_t d, float eps, const float* gamma,
-                              const float* beta, void* y, int32_t dtype, void* stream) {
-  VGEN_REQUIRE(dtype == VGEN_BF16 || dtype == VGEN_F16 || dtype == VGEN_F32, "layernorm: dtype");
-  VGEN_REQUIRE(d > 0 && d % 4 == 0 && d <= 64 * 4 * LN_MAX_SLOTS, "layernorm: d=%d", d);
-  VGEN_REQUIRE(vgen_aligned16(x) && vgen_aligned16(y) && vgen_aligned16(gamma) &&
-                   vgen_aligned16(beta),
-               "layernorm: alignment");
+extern "C" int vgen_layernorm(const float* x, int64_t M, int32_t d, float eps, const float* gamma, const float* beta, void* y,
+                              int32_t dtype, void* stream) {
+  const int rc = ln_validate(x, M, d, gamma, beta, y, dtype);
+  if (rc) return rc;
   if (M <= 0) return 0;
-  VGEN_REQUIRE(M < (1LL << 32), "layernorm: M too large");
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == VGEN_F32) {
-    if (d <= 512) launch_ln<F32Out, 16>(x, M, d, eps, gamma, beta, y, s);
-    else if (d <= 1024) launch_ln<F32Out, 32>(x, M, d, eps, gamma, beta, y, s);
-    else launch_ln<F32Out, 64>(x, M, d, eps, gamma, beta, y, s);
-    return vgen_check_launch("layernorm");
-  }
-  if (dtype == VGEN_BF16) dispatch_ln<BF16>(x, M, d, eps, gamma, beta, (uint16_t*)y, s);
-  else dispatch_ln<F16>(x, M, d, eps, gamma, beta, (uint16_t*)y, s);
+  const LnPlan p = ln_plan(M, d, dtype);
+  kLnLaunch[dtype][p.lpr >> 5][p.ns == 0 ? 0 : p.ns == 5 ? 1 : 2](x, M, d, eps, gamma, beta, y, p.grid, (hipStream_t)stream);
   return vgen_check_launch("layernorm");
 }

@@ -14,18 +14,7 @@
 #include <new>
 #include <vector>
 
-void vgen_set_error(const char* fmt, ...);   // cabi.cpp (the stand-alone driver brings its own)
-
-// common.h's VGEN_REQUIRE / vgen_aligned16, restated: that header pulls in the HIP runtime
-#define VGEN_REQUIRE(cond, ...)    \
-  do {                             \
-    if (!(cond)) {                 \
-      vgen_set_error(__VA_ARGS__); \
-      return VGEN_E_BADARG;        \
-    }                              \
-  } while (0)
-
-static inline bool vgen_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+#include "host_check.h"
 
 namespace {
 

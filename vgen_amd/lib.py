@@ -70,6 +70,8 @@ SYMBOLS = {
     "vgen_tapgemm": (C.c_int, [C.POINTER(TapGemmArgs), _vp]),
     "vgen_tapgemm_query_plan": (C.c_int, [C.POINTER(TapGemmArgs), _vp]),
     "vgen_tapgemm_set_plans": (C.c_int, [_vp, _i32]),
+    "vgen_groupnorm_query_plan": (C.c_int, [_i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "vgen_layernorm_query_plan": (C.c_int, [_i64, _i32, _i32, _vp]),
     "vgen_attention": (C.c_int, [C.POINTER(AttnArgs), _vp]),
     "vgen_attention_d80": (C.c_int, [C.POINTER(AttnArgs), _vp]),
     "vgen_softmax_rows": (C.c_int, [_vp, _i64, _i32, _i64, _f32, _vp, _i64, _i32, _vp]),
