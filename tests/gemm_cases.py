@@ -1,0 +1,802 @@
+"""Tap-GEMM / panel-GEMM edge cases: operands, the fp64 reference, a DERIVED per-element bound, the case table, CPU models of
+the kernels' arithmetic (with switchable modelled mistakes) and the epilogue-path predicates of csrc/tapgemm.hip.  Pure torch
+on the CPU; shared by tests/test_tapgemm_edges.py (CPU and GPU tests).  Measured values: DESIGN.md section 3.1.
+
+Reference: the ABI formula of include/vgen_hip.h evaluated in float64 on the SAME 16-bit operands,
+
+    out[m, n] = epi( sum_tap sum_c A[src(m, tap), c] W[n, tap C1 + c] + sum_c A2[m, c] W[n, taps C1 + c] )
+
+with the source rows written here in image / frame terms (NCHW pad + strided slices, a zero frame at both ends of the F
+axis) — not the row-index arithmetic of oracle/abi_emulator.py or of the kernel.  Dual-W: A (W_hi + W_lo)^T.
+
+Bound per output element (u = 2^-23: ONE ulp of fp32, not half, so an MFMA adder that truncates stays inside):
+
+    e32 = (K_exec + 4) u (sum |a| |w| + |bias| + |rowbias| + |residual|)       K_exec = products per element, 2 K for dual-W
+
+K_exec + 3 additions in ANY order (Higham's gamma_n with n u << 1) — every split-K factor, block shape and K-tile order.
+  fp32 output     |out - ref| <= e32
+  16-bit output   r16(ref - e32) <= out <= r16(ref + e32): rounding is monotone (the idiom of adapter_cases)
+  split_out       hi as above; |hi + lo - ref| <= e32 + 2^-17 |ref| (bf16) / 2^-22 |ref| (fp16): lo = r16(v - hi) leaves a
+                  quarter ulp of an ulp of hi (test_cast_split_is_the_emulators_bits)
+  GEGLU           value v and gate s carry their own e32 (e_v, e_s); g = gelu_erf(s):
+                     e_g = 1.13 e_s + 20 2^-24 |s| + 2 2^-24 |g|                (adapter_cases: max gelu' = 1.13, erff term)
+                     e   = e_v (|g| + e_g) + |v| e_g + u (|v g| + |ref|)        product and residual-add roundings
+                  the residual is added AFTER the gate and enters through u |ref| only
+  colstats        per 64-row slab against fp64 sums of the kernel's OWN fp32 output x: 66 u sum|x| / 66 u sum x^2 (64 addends
+                  + one product each): the product and the statistics fail separately
+Statistic: worst = max |err| / bound <= 1 (interval checks count as 0 inside, inf outside).  `int_exact` needs no bound at all:
+every partial sum is an integer below 2^24, the output must be BIT-equal.  Nothing here is fitted to what a device returns."""
+from __future__ import annotations
+
+import math
+import zlib
+from dataclasses import dataclass
+
+import torch
+import torch.nn.functional as Fn
+
+U = 2.0 ** -23
+U24 = 2.0 ** -24
+GELU_LIP = 1.13                      # adapter_cases.GELU_LIP
+DTS = {"bf16": torch.bfloat16, "fp16": torch.float16}
+HILO = {torch.bfloat16: 2.0 ** -17, torch.float16: 2.0 ** -22}
+U16 = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -12}      # half an ulp, relative, at the bottom of a binade
+FAMILIES = ("int_exact", "scaled")
+GUARD = 8                            # guard rows: 8 rows of any leading dimension keep 16-byte alignment for 16-bit and fp32
+CS_ROWS = 64
+CS_C = 66.0
+
+
+def _gen(*key):
+    return torch.Generator("cpu").manual_seed(zlib.crc32(repr(key).encode()) & 0x7FFFFFFF)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Spec:
+    name: str
+    M: int
+    N: int
+    C1: int
+    mode: str = "lin"               # lin | conv | temp
+    C2: int = 0
+    geom: tuple = ()                # conv: (nimg, Hi, Wi, Ho, Wo, stride, pad, ups, crop_t); temp: (B, F, S)
+    bias: bool = True
+    rb: int = 0                     # rows_per_rb (0: no row bias)
+    rb_pad: int = 8                 # rowbias_ld = N + rb_pad
+    res: bool = False
+    ldr: int = 0                    # 0: n_out
+    out16: bool = False
+    geglu: bool = False
+    cs: bool = False
+    split_out: bool = False
+    dualw: bool = False
+    a_pad: int = 0
+    w_pad: int = 0
+    ldo: int = 0                    # 0: dense
+    col_off: int = 0
+    splits: tuple = ()              # split-K factors to run besides 1, 2 and the largest legal
+    sweep: bool = True              # run under every plan the planner confirms (False: the planner's own choice only)
+
+    @property
+    def taps(self):
+        return {"lin": 1, "conv": 9, "temp": 3}[self.mode]
+
+    @property
+    def K(self):
+        return self.taps * self.C1 + self.C2
+
+    @property
+    def n_out(self):
+        return self.N // 2 if self.geglu else self.N
+
+    @property
+    def w_out(self):
+        return 2 * self.n_out if self.split_out else self.n_out
+
+    @property
+    def src_rows(self):
+        return self.geom[0] * self.geom[1] * self.geom[2] if self.mode == "conv" else self.M
+
+    @property
+    def ld_out(self):
+        return self.ldo or self.w_out
+
+    @property
+    def ld_res(self):
+        return self.ldr or self.n_out
+
+    @property
+    def kexec(self):
+        return self.K * (2 if self.dualw else 1)
+
+
+def conv(name, nimg, Hi, Wi, Ho, Wo, N, C1, stride=1, pad=1, ups=0, crop=0, **kw):
+    return Spec(name, nimg * Ho * Wo, N, C1, mode="conv", geom=(nimg, Hi, Wi, Ho, Wo, stride, pad, ups, crop), **kw)
+
+
+def temp(name, B, F, S, N, C1, **kw):
+    return Spec(name, B * F * S, N, C1, mode="temp", geom=(B, F, S), **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the case table: the smallest shapes that reach each edge
+def _linear_specs():
+    s = [
+        Spec("lin_1x64x64", 1, 64, 64),
+        Spec("lin_257x192x128_bias_res", 257, 192, 128, res=True),                       # M = BM + 1: one live row in tile 2
+        Spec("lin_129x80x192_out16", 129, 80, 192, out16=True),                          # N % 32 == 16: pair_ok false, live fragment
+        Spec("lin_65x128x64_out16_ldo132", 65, 128, 64, out16=True, ldo=132),            # vectorisable, ldo % 8 != 0: 8-byte stores
+        Spec("lin_130x3x128_res_ldr3", 130, 3, 128, res=True, ldr=3),                    # scalar epilogue
+        Spec("lin_130x3x128_res_ldr3_out16", 130, 3, 128, res=True, ldr=3, out16=True),
+        Spec("lin_70x100x256_view_ldo104_off4", 70, 100, 256, ldo=104, col_off=4),
+        Spec("lin_300x320x192_rb7", 300, 320, 192, rb=7, rb_pad=8),
+        Spec("lin_300x320x192_rb7_out16", 300, 320, 192, rb=7, rb_pad=8, out16=True),
+        Spec("lin_200x192x128_views_lda_ldw", 200, 192, 128, a_pad=64, w_pad=128, res=True),
+        # K of exactly one, two and three ring stages on the BK = 32 shapes (and 1 K-tile on BK = 64)
+        Spec("lin_100x128x64_K1tile", 100, 128, 64),
+        Spec("lin_100x128x128_K2tiles", 100, 128, 128, out16=True),
+        Spec("lin_100x64x192_K3tiles", 100, 64, 192, res=True),
+        Spec("geglu_130x64_f32", 130, 64, 128, geglu=True),
+        Spec("geglu_130x128_out16_res", 130, 128, 192, geglu=True, out16=True, res=True),
+        Spec("geglu_257x256_out16", 257, 256, 128, geglu=True, out16=True),
+        Spec("geglu_257x256_f32_res", 257, 256, 128, geglu=True, res=True),
+        # second K segment, 9 K-tiles: split 2 cuts at K-tile 4 — exactly the C1 | C2 edge (4 | 5), inside segment 1 (5 | 4)
+        Spec("seg_100x128_256+320", 100, 128, 256, C2=320, res=True),
+        Spec("seg_100x128_320+256", 100, 128, 320, C2=256, out16=True),
+        Spec("seg_100x128_256+256", 100, 128, 256, C2=256),
+        Spec("cs_63x128", 63, 128, 128, cs=True, rb=16),
+        Spec("cs_65x320", 65, 320, 64, cs=True, rb=13, res=True),
+        Spec("cs_300x128", 300, 128, 192, cs=True, rb=50, res=True),
+        Spec("cs_300x320", 300, 320, 128, cs=True, rb=7),
+        Spec("splitout_130x96", 130, 96, 128, out16=True, split_out=True, res=True),
+        Spec("splitout_130x160", 130, 160, 128, out16=True, split_out=True, rb=9, rb_pad=4),
+        Spec("limit_2x4xK131008", 2, 4, 131008, sweep=False),                            # dead W rows walk the zero region to its last byte
+        Spec("dw_limit_2x4xK65472", 2, 4, 65472, dualw=True, sweep=False),
+    ]
+    sk = dict(M=100, N=128, C1=1024, splits=(2, 3, 4))
+    s += [Spec("splitk_f32", **sk), Spec("splitk_out16", out16=True, **sk), Spec("splitk_rb", rb=33, **sk),
+          Spec("splitk_res", res=True, **sk), Spec("splitk_geglu", geglu=True, out16=True, res=True, **sk),
+          Spec("splitk_geglu_f32", geglu=True, **sk)]
+    return s
+
+
+def _conv_specs():
+    return [
+        conv("conv_1x1_nimg5", 5, 1, 1, 1, 1, 64, 64),
+        conv("conv_3x5_nimg7_rb15", 7, 3, 5, 3, 5, 128, 64, rb=15),                       # hw = 15 never divides a tile
+        conv("conv_s2p1_7x5", 3, 7, 5, 4, 3, 64, 64, stride=2, pad=1),
+        conv("conv_s2p0_8x6", 3, 8, 6, 4, 3, 64, 64, stride=2, pad=0, out16=True),
+        conv("conv_s2p0_7x5", 3, 7, 5, 3, 2, 64, 64, stride=2, pad=0),
+        conv("conv_ups_3x2", 3, 3, 2, 6, 4, 64, 64, ups=1, res=True),
+        conv("conv_ups_crop_4x3", 3, 4, 3, 6, 6, 64, 64, ups=1, crop=1),
+        conv("conv_skipseg", 2, 6, 5, 6, 5, 128, 64, C2=128, out16=True),
+        conv("conv_C64_KT9", 5, 3, 5, 3, 5, 64, 64, res=True, splits=(2,)),
+        conv("conv_C192_KT27", 5, 3, 5, 3, 5, 128, 192, rb=15, splits=(2, 3, 4, 5, 6)),   # split boundaries mid-tap
+    ]
+
+
+def _temporal_specs():
+    return [
+        temp("temp_3x1x7", 3, 1, 7, 64, 64),
+        temp("temp_2x2x5", 2, 2, 5, 64, 64, res=True),
+        temp("temp_3x5x24", 3, 5, 24, 128, 64, out16=True),                              # tiles straddle batches
+        temp("temp_C192_split2", 3, 5, 24, 128, 192, res=True, splits=(2,)),
+    ]
+
+
+def _dualw_specs():
+    return [
+        Spec("dw_lin_257x192x128_res", 257, 192, 128, res=True, dualw=True, sweep=False),
+        Spec("dw_splitk_100x128x1024", 100, 128, 1024, dualw=True, sweep=False),
+        # the planner's cost model gives a dual-W launch the 256-row "pp" shape only where "pp128" needs a second round of
+        # tiles: 2 x 129 tiles of 128 rows > 256 CUs >= 129 tiles of 256 rows
+        Spec("dw_lin_129x16512x64_out16", 129, 16512, 64, out16=True, dualw=True, sweep=False),
+        conv("dw_conv_3x5_nimg7_rb15", 7, 3, 5, 3, 5, 128, 64, rb=15, dualw=True, sweep=False),
+        temp("dw_temp_3x5x24", 3, 5, 24, 128, 64, out16=True, dualw=True, sweep=False),
+    ]
+
+
+def _panel_specs():
+    s = []
+    for M in (2048, 2049, 2081):
+        s.append(Spec(f"panel_{M}x320_f32_res", M, 320, 320, res=True))
+        s.append(Spec(f"panel_{M}x160_out16", M, 160, 320, out16=True))
+    s += [Spec("panel_2049x160_f32_res", 2049, 160, 320, res=True), Spec("panel_2081x320_out16", 2081, 320, 320, out16=True),
+          Spec("panel_2081x640_geglu", 2081, 640, 320, geglu=True, out16=True),
+          Spec("panel_2049x640_geglu_res", 2049, 640, 320, geglu=True, out16=True, res=True),
+          Spec("panel_dw_2081x320_f32_res", 2081, 320, 320, res=True, dualw=True, sweep=False),
+          Spec("panel_dw_2049x160_out16", 2049, 160, 320, out16=True, dualw=True, sweep=False),
+          Spec("panel_k640_2081x80_out16", 2081, 80, 640, out16=True),
+          Spec("panel_k640_2049x160_f32_res", 2049, 160, 640, res=True)]
+    return s
+
+
+def specs():
+    s = _linear_specs() + _conv_specs() + _temporal_specs() + _dualw_specs() + _panel_specs()
+    assert len({x.name for x in s}) == len(s)
+    return s
+
+
+SPECS = {s.name: s for s in specs()}
+PANEL_NAMES = tuple(s.name for s in _panel_specs())
+DUALW_NAMES = tuple(s.name for s in specs() if s.dualw)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# operands.  Live tensors are slices of NaN-poisoned storage: A rows outside the live source rows, A columns >= C1, W rows
+# >= N, W columns >= K, the padding columns of the row bias and of the residual.
+def _scales(n, lo, hi):
+    """n exponents in [lo, hi]: the two ends first, then a golden-ratio sequence — any n >= 2 spans the whole range and
+    neighbours are never close."""
+    e = lo + (hi - lo) * ((torch.arange(n, dtype=torch.float64) * 0.6180339887498949) % 1.0)
+    if n >= 2:
+        e[0], e[1] = lo, hi
+    return (2.0 ** e).float()
+
+
+def _ints(g, shape, k):
+    return torch.randint(-k, k + 1, shape, generator=g).float()
+
+
+def _framed(live, pad_cols=0, dtype=None):
+    """live [R, C] inside NaN storage [R + 2 GUARD, C + pad_cols]; returns (storage, live view)."""
+    R, Cn = live.shape
+    st = torch.full((R + 2 * GUARD, Cn + pad_cols), float("nan"), dtype=dtype or live.dtype)
+    st[GUARD:GUARD + R, :Cn] = live
+    return st, st[GUARD:GUARD + R, :Cn]
+
+
+@dataclass
+class Operands:
+    spec: Spec
+    dt: torch.dtype
+    family: str
+    A: torch.Tensor                 # live view [src_rows, C1] (16-bit) of A_store
+    A_store: torch.Tensor
+    W: torch.Tensor                 # live view [N, K]; dual-W: the [N, 2 K] interleaved operand
+    W_store: torch.Tensor
+    W_hi: torch.Tensor = None       # dual-W terms [N, K]
+    W_lo: torch.Tensor = None
+    A2: torch.Tensor = None
+    A2_store: torch.Tensor = None
+    bias: torch.Tensor = None
+    rowbias: torch.Tensor = None    # live view [nrb, N]
+    rb_store: torch.Tensor = None
+    residual: torch.Tensor = None   # live view [M, n_out]
+    res_store: torch.Tensor = None
+    row_scale: torch.Tensor = None
+    col_scale: torch.Tensor = None
+
+
+def operands(spec, family, dt, seed=0):
+    g = _gen("gemm", spec.name, family, str(dt), seed)
+    M, N, K, C1, C2 = spec.M, spec.N, spec.K, spec.C1, spec.C2
+    R = spec.src_rows
+    nrb = (M + spec.rb - 1) // spec.rb if spec.rb else 0
+    rs = cs = None
+    if family == "int_exact":
+        ka = 1 if spec.cs else 3                                  # column statistics: magnitudes in {-1, 0, 1}
+        kb = 1 if spec.cs else 8
+        a, a2 = _ints(g, (R, C1), ka), (_ints(g, (M, C2), ka) if C2 else None)
+        w = _ints(g, (N, K), ka)
+        w_lo = _ints(g, (N, K), 3) if spec.dualw else None
+        if spec.split_out:          # one sign: the sums reach 256 .. 330, where odd integers need the second bf16 term (lo != 0)
+            a, w = a.abs(), w.abs()
+        if spec.dualw:
+            w = 8 * w                                             # W_hi = 8 i, W_lo = j: both terms live, every product an integer
+        bias = _ints(g, (N,), kb)
+        if spec.geglu:                                            # gate: zero weights, bias in [8, 16]: erf saturates to exactly 1
+            gate = (torch.arange(N) % 32) >= 16
+            w[gate] = 0
+            if w_lo is not None:
+                w_lo[gate] = 0
+            bias[gate] = torch.randint(8, 17, (int(gate.sum()),), generator=g).float()
+        rb = _ints(g, (nrb, N), kb) if nrb else None
+        res = _ints(g, (M, spec.n_out), kb) if spec.res else None
+    elif family in ("scaled", "gauss"):
+        sc = family == "scaled"
+        rs = _scales(R, -4, 4) if sc else torch.ones(R)
+        cs = _scales(N, -3, 3) if sc else torch.ones(N)
+        a = torch.randn(R, C1, generator=g) * rs.view(R, 1)
+        # the row scale of an OUTPUT row: that of its own source row (linear / temporal) — conv rows mix 9 source rows
+        ors = rs[:M] if spec.mode != "conv" else _scales(M, -4, 4) if sc else torch.ones(M)
+        a2 = torch.randn(M, C2, generator=g) * ors.view(M, 1) if C2 else None
+        w32 = torch.randn(N, K, generator=g) / K ** 0.5 * cs.view(N, 1)
+        w = w32
+        w_lo = None
+        if spec.dualw:
+            w = w32.to(dt).float()
+            w_lo = (w32 - w).to(dt).float()
+        bias = torch.randn(N, generator=g) * cs
+        rb = torch.randn(nrb, N, generator=g) * cs.view(1, N) if nrb else None
+        if spec.res:
+            ocs = cs if not spec.geglu else cs.view(-1, 2, 16)[:, 0].reshape(-1)
+            res = torch.randn(M, spec.n_out, generator=g) * ors.view(M, 1) * ocs.view(1, -1)
+        else:
+            res = None
+    else:
+        raise ValueError(family)
+    A_store, A = _framed(a.to(dt), spec.a_pad)
+    op = Operands(spec, dt, family, A, A_store, None, None, row_scale=rs, col_scale=cs)
+    if spec.dualw:
+        hi, lo = w.to(dt), w_lo.to(dt)
+        dw = torch.stack([hi.view(N, K // 64, 64), lo.view(N, K // 64, 64)], 2).reshape(N, 2 * K)
+        op.W_store, op.W = _framed(dw, spec.w_pad)
+        op.W_hi, op.W_lo = hi, lo
+    else:
+        op.W_store, op.W = _framed(w.to(dt), spec.w_pad)
+    if C2:
+        op.A2_store, op.A2 = _framed(a2.to(dt), 0)
+    op.bias = bias if spec.bias or spec.geglu else None
+    if nrb:
+        st = torch.full((nrb, N + spec.rb_pad), float("nan"))
+        off = 4 if spec.rb_pad >= 4 else 0
+        st[:, off:off + N] = rb
+        op.rb_store, op.rowbias = st, st[:, off:off + N]
+    if spec.res:
+        op.res_store, op.residual = _framed(res, spec.ld_res - spec.n_out)
+    return op
+
+
+def family_property(op):
+    """The defining property of the operand family, asserted in fp64 at every shape used."""
+    sp = op.spec
+    assert bool(torch.isfinite(op.A.float()).all()) and bool(torch.isfinite(op.W.float()).all())
+    assert bool(torch.isnan(op.A_store[:GUARD].float()).all()) and bool(torch.isnan(op.A_store[-GUARD:].float()).all())
+    assert bool(torch.isnan(op.W_store[-GUARD:].float()).all())
+    if sp.a_pad:
+        assert bool(torch.isnan(op.A_store[:, sp.C1:].float()).all())
+    if sp.w_pad:
+        assert bool(torch.isnan(op.W_store[:, op.W.shape[1]:].float()).all())
+    if op.family == "int_exact":
+        r = reference(op)
+        mag = r.absacc
+        assert float(mag.max()) < 2.0 ** 24, float(mag.max())
+        assert float(r.ref.abs().max()) <= 65504, float(r.ref.abs().max())
+        for t in (op.A, op.W, op.bias, op.rowbias, op.residual, op.A2):
+            if t is not None:
+                assert bool((t.double() == t.double().round()).all())
+        assert bool((r.ref == r.ref.round()).all())
+        if sp.cs:                                                 # slab sums of squares stay exact in fp32 in any order
+            x = r.ref
+            pad = (-sp.M) % CS_ROWS
+            q = torch.cat([x, torch.zeros(pad, sp.N, dtype=x.dtype)]).view(-1, CS_ROWS, sp.N).pow(2).sum(1)
+            assert float(q.max()) < 2.0 ** 24, float(q.max())
+        if sp.geglu:
+            assert float(r.gate.min()) >= 8 and bool((torch.erf(r.gate.float() * 0.7071067811865476) == 1).all())
+    elif op.family == "scaled":
+        span = lambda s: float(s.max() / s.min())      # noqa: E731
+        assert sp.N < 2 or span(op.col_scale) >= 2.0 ** 6 * (1 - 1e-6), span(op.col_scale)
+        assert op.row_scale.numel() < 2 or span(op.row_scale) > 2.0 ** 6, span(op.row_scale)
+        # and the scales are IN the operands: row norms of A follow the row scale within a factor 2
+        if sp.C1 >= 64:
+            rn = op.A.double().pow(2).mean(1).sqrt() / op.row_scale.double()
+            assert float(rn.min()) > 0.5 and float(rn.max()) < 2.0, (float(rn.min()), float(rn.max()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# source rows in image / frame terms
+def tap_patches(spec, X, defect=None):
+    """X [src_rows, C] -> the `taps` matrices [M, C] whose row m is the source row of output row m under that tap (zeros
+    where the tap leaves the image / the clip).  conv: NCHW, nearest 2x upsample, crop, zero pad, strided slices.
+    temporal: [B, F, S, C] with a zero frame at both ends of F."""
+    Cn = X.shape[1]
+    if spec.mode == "lin":
+        return [X[:spec.M]]
+    if spec.mode == "conv":
+        nimg, Hi, Wi, Ho, Wo, stride, pad, ups, crop = spec.geom
+        img = X.view(nimg, Hi, Wi, Cn).permute(0, 3, 1, 2)
+        if ups:
+            img = img.repeat_interleave(2, 2).repeat_interleave(2, 3)
+        if crop:
+            img = img[:, :, crop:img.shape[2] - crop]
+        Hv, Wv = img.shape[2:]
+        eh, ew = (Ho - 1) * stride + 3, (Wo - 1) * stride + 3       # extent the taps reach, from -pad
+        pb, pr = max(eh - pad - Hv, 0) + 2, max(ew - pad - Wv, 0) + 2
+        if defect == "clamp_pad":                                     # a padding tap reads the clamped neighbour pixel
+            P = Fn.pad(img, (pad, pr, pad, pb), mode="replicate") if img.dtype != torch.float64 else \
+                Fn.pad(img.float(), (pad, pr, pad, pb), mode="replicate").double()
+        else:
+            P = Fn.pad(img, (pad, pr, pad, pb))
+        out = []
+        for ky in range(3):
+            for kx in range(3):
+                y0, x0 = (kx, ky) if defect == "kykx_transposed" else (ky, kx)
+                v = P[:, :, y0:y0 + (Ho - 1) * stride + 1:stride, x0:x0 + (Wo - 1) * stride + 1:stride]
+                out.append(v.permute(0, 2, 3, 1).reshape(spec.M, Cn))
+        return out
+    B, F, S = spec.geom
+    if defect == "temporal_cross_batch":                              # frame f - 1 / f + 1 of the GLOBAL frame index
+        V = Fn.pad(X.view(1, B * F, S, Cn), (0, 0, 0, 0, 1, 1))
+        return [V[:, k:k + B * F].reshape(spec.M, Cn) for k in range(3)]
+    V = Fn.pad(X.view(B, F, S, Cn), (0, 0, 0, 0, 1, 1))
+    return [V[:, k:k + F].reshape(spec.M, Cn) for k in range(3)]
+
+
+def _w_terms(op, dtype):
+    if op.spec.dualw:
+        return op.W_hi.to(dtype) + op.W_lo.to(dtype)                  # exact in fp64; fp32: the model's own sum
+    return op.W.to(dtype)
+
+
+def _degeglu(t):
+    """packed columns [.., N] -> (value [.., N/2], gate [.., N/2]): blocks of [16 value | 16 gate]"""
+    v = t.reshape(t.shape[0], -1, 2, 16)
+    return v[:, :, 0].reshape(t.shape[0], -1), v[:, :, 1].reshape(t.shape[0], -1)
+
+
+def gelu64(s):
+    return 0.5 * s * (1.0 + torch.erf(s * 0.7071067811865476))
+
+
+@dataclass
+class Ref:
+    ref: torch.Tensor              # fp64 [M, n_out]
+    e32: torch.Tensor              # the fp32 part of the bound, [M, n_out]
+    absacc: torch.Tensor           # sum |a| |w| + |bias| + |rowbias| + |residual| per ACCUMULATOR element [M, N] (+ residual where not gated)
+    gate: torch.Tensor = None
+
+
+def reference(op):
+    sp = op.spec
+    W = _w_terms(op, torch.float64)
+    acc = torch.zeros(sp.M, sp.N, dtype=torch.float64)
+    mag = torch.zeros_like(acc)
+    for t, P in enumerate(tap_patches(sp, op.A.double())):
+        Wt = W[:, t * sp.C1:(t + 1) * sp.C1]
+        acc += P @ Wt.t()
+        mag += P.abs() @ Wt.abs().t()
+    if sp.C2:
+        Wt = W[:, sp.taps * sp.C1:]
+        acc += op.A2.double() @ Wt.t()
+        mag += op.A2.double().abs() @ Wt.abs().t()
+    if sp.dualw:                                                      # |w_hi| + |w_lo| >= |w_hi + w_lo|: the larger magnitude
+        Wa = op.W_hi.double().abs() + op.W_lo.double().abs() - W.abs()
+        for t, P in enumerate(tap_patches(sp, op.A.double().abs())):
+            mag += P @ Wa[:, t * sp.C1:(t + 1) * sp.C1].t()
+        if sp.C2:
+            mag += op.A2.double().abs() @ Wa[:, sp.taps * sp.C1:].t()
+    if op.bias is not None:
+        acc += op.bias.double()
+        mag += op.bias.double().abs()
+    if op.rowbias is not None:
+        idx = torch.arange(sp.M) // sp.rb
+        acc += op.rowbias.double()[idx]
+        mag += op.rowbias.double().abs()[idx]
+    res = op.residual.double() if op.residual is not None else None
+    ku = (sp.kexec + 4) * U
+    if sp.geglu:
+        v, s = _degeglu(acc)
+        mv, ms = _degeglu(mag)
+        e_v, e_s = ku * mv, ku * ms
+        # int_exact: gates >= 8, where erff is exactly 1 and gelu(s) = s in fp32 (fp64's erf(8 / sqrt 2) is 1 - 1.2e-15: the
+        # INTEGER result is v s)
+        g = s if op.family == "int_exact" else gelu64(s)
+        e_g = GELU_LIP * e_s + 20 * U24 * s.abs() + 2 * U24 * g.abs()
+        ref = v * g
+        e = e_v * (g.abs() + e_g) + v.abs() * e_g + U * ref.abs()
+        if res is not None:
+            ref = ref + res
+            e = e + U * ref.abs()
+        return Ref(ref, e, mag, s)
+    if res is not None:
+        acc = acc + res
+        mag = mag + res.abs()
+    return Ref(acc, ku * mag, mag)
+
+
+def r16(v, dt):
+    """fp64 -> fp32 -> 16 bit, both to nearest even: monotone, and the identity on what a kernel can hold in fp32"""
+    return v.float().to(dt)
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+def check(op, ref, out, lo=None):
+    """out [M, n_out] (fp32 or 16-bit; `lo` the second term of split_out) against the reference.  Returns (worst, bad mask
+    [M, n_out], messages).  int_exact: bit equality, worst is 0 or inf."""
+    sp, dt = op.spec, op.dt
+    msgs = []
+    o = out.double()
+    finite = torch.isfinite(o)
+    if op.family == "int_exact":
+        want = ref.ref.float() if out.dtype == torch.float32 else r16(ref.ref, dt)
+        bad = bits(out) != bits(want)
+        # (integer sums that start at +0 never give -0 in round-to-nearest: x + (-x) = +0, so the zeros agree in bits too)
+        if lo is not None:
+            wl = (ref.ref.float() - want.float()).to(dt)
+            bl = bits(lo) != bits(wl)
+            if bool(bl.any()):
+                msgs.append(f"split_out lo: {int(bl.sum())} elements differ from the bits of r16(v - hi)")
+            bad = bad | bl
+        return (math.inf if bool(bad.any()) else 0.0), bad, msgs
+    if out.dtype == torch.float32:
+        err = (o - ref.ref).abs()
+        ratio = torch.where(ref.e32 > 0, err / ref.e32.clamp_min(1e-300), torch.where(err > 0, math.inf, 0.0))
+    else:
+        lo_b, hi_b = r16(ref.ref - ref.e32, dt).double(), r16(ref.ref + ref.e32, dt).double()
+        inside = (o >= lo_b) & (o <= hi_b)
+        err = (o - ref.ref).abs()
+        # pass / fail is the interval; the figure recorded inside it is the error in units of e32 + half an ulp of the output
+        ratio = torch.where(inside, (err / (ref.e32 + U16[dt] * ref.ref.abs()).clamp_min(1e-300)).clamp(max=1.0),
+                            torch.full_like(err, math.inf))
+    ratio = torch.where(finite, ratio, torch.full_like(ratio, math.inf))
+    if lo is not None:
+        e2 = (o + lo.double() - ref.ref).abs()
+        b2 = ref.e32 + HILO[dt] * ref.ref.abs()
+        r2 = torch.where(torch.isfinite(lo.double()), e2 / b2.clamp_min(1e-300), torch.full_like(e2, math.inf))
+        if bool((r2 > 1).any()):
+            msgs.append(f"split_out hi + lo: worst {float(r2.max()):.3g} of e32 + {HILO[dt]:.2g} |ref|")
+        ratio = torch.maximum(ratio, r2)
+    return (float(ratio.max()) if ratio.numel() else 0.0), ~(ratio <= 1), msgs
+
+
+def check_colstats(spec, out32, cs, exact=False):
+    """cs [ceil(M / 64), 2, N] against fp64 slab sums of the kernel's own fp32 output.  Returns (worst, messages)."""
+    x = out32.double()
+    pad = (-spec.M) % CS_ROWS
+    xp = torch.cat([x, torch.zeros(pad, spec.N, dtype=x.dtype)]).view(-1, CS_ROWS, spec.N)
+    s, q, a = xp.sum(1), xp.pow(2).sum(1), xp.abs().sum(1)
+    got = cs.double()
+    if exact:
+        bad = (got[:, 0] != s) | (got[:, 1] != q)
+        return (math.inf if bool(bad.any()) else 0.0), ([f"colstats: {int(bad.sum())} slab sums not exact"] if bool(bad.any()) else [])
+    w = 0.0
+    msgs = []
+    for name, g_, want, bnd in (("sums", got[:, 0], s, CS_C * U * a), ("squares", got[:, 1], q, CS_C * U * q)):
+        err = (g_ - want).abs()
+        r = torch.where(bnd > 0, err / bnd.clamp_min(1e-300), torch.where(err > 0, math.inf, 0.0))
+        r = torch.where(torch.isfinite(g_), r, torch.full_like(r, math.inf))
+        if bool((r > 1).any()):
+            i = (r > 1).nonzero()[:5].tolist()
+            msgs.append(f"colstats {name}: worst {float(r.max()):.3g} at (slab, n) {i}")
+        w = max(w, float(r.max()))
+    return w, msgs
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the streaming shapes as csrc/tapgemm_plan.h states them: name, BM, BK, waves along M x N (index = enum Shape)
+SHAPES = {0: ("pp", 256, 64, 4, 2), 1: ("dual", 256, 32, 2, 2), 2: ("pp128", 128, 64, 4, 2), 3: ("panel", 32, 64, 8, 1),
+          4: ("pp256", 256, 32, 4, 2), 5: ("q128", 128, 32, 2, 2)}
+STREAMING = (0, 1, 2, 4, 5)
+BNS = (64, 128, 160, 256)
+
+
+def describe(spec, m, n, plan):
+    """Where output element (m, n) lives: tile coordinates under the plan, source image / frame, the tap neighbourhood."""
+    name, bm, _, wm, wn = SHAPES[plan[0]]
+    bn = plan[1]
+    pn = n if not spec.geglu else 32 * (n // 16) + n % 16
+    s = f"tile ({m // bm}, {pn // bn}) row {m % bm} col {pn % bn} of {name} {bm}x{bn} split {plan[2]}"
+    if plan[0] != 3:
+        wtm, wtn = bm // wm, bn // wn
+        s += f", wave ({m % bm // wtm}, {pn % bn // wtn}) frag ({m % wtm // 16}, {pn % wtn // 16})"
+    if spec.mode == "conv":
+        nimg, Hi, Wi, Ho, Wo, stride, pad, ups, crop = spec.geom
+        img, rem = divmod(m, Ho * Wo)
+        oy, ox = divmod(rem, Wo)
+        Hv, Wv = (Hi << ups) - 2 * crop, Wi << ups
+        taps = "".join("." if 0 <= oy * stride + ky - pad < Hv and 0 <= ox * stride + kx - pad < Wv else "0"
+                       for ky in range(3) for kx in range(3))
+        s += f"; image {img} pixel ({oy}, {ox}) of {Ho}x{Wo}, taps in range (ky kx row-major) {taps[:3]}|{taps[3:6]}|{taps[6:]}"
+    elif spec.mode == "temp":
+        B, F, S = spec.geom
+        b, r = divmod(m, F * S)
+        f, p = divmod(r, S)
+        s += f"; batch {b} frame {f} of {F} pixel {p}, taps in range {'.' if f > 0 else '0'}.{'.' if f < F - 1 else '0'}"
+    if spec.rb:
+        s += f"; row-bias row {m // spec.rb}"
+    return s
+
+
+def offenders(op, ref, out, bad, plan, limit=10):
+    sp = op.spec
+    o = out.double()
+    err = (o - ref.ref).abs() / ref.e32.clamp_min(1e-300)
+    err = torch.where(bad, torch.where(torch.isfinite(err), err, torch.full_like(err, 1e300)), torch.zeros_like(err))
+    lines = [f"{int(bad.sum())} of {bad.numel()} elements outside, {sp.name} {op.family} {op.dt} plan {plan}"]
+    for i in err.flatten().argsort(descending=True)[:limit].tolist():
+        m, n = divmod(i, sp.n_out)
+        if not bool(bad[m, n]):
+            break
+        lines.append(f"  ({m}, {n}): out {float(o[m, n]):.8g} ref {float(ref.ref[m, n]):.8g} |err| / e32 {float(err[m, n]):.3g} — "
+                     + describe(sp, m, n, plan))
+    rows, cols = bad.any(1).nonzero().flatten().tolist(), bad.any(0).nonzero().flatten().tolist()
+    lines.append(f"  rows hit: {len(rows)} {rows[:12]}; columns hit: {len(cols)} {cols[:12]}")
+    return "\n".join(lines)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the epilogue of tapgemm_kernel as predicates (csrc/tapgemm.hip; the line of each decision is cited)
+def kernel_vec(spec):
+    """tapgemm.hip:338 `vec`: every epilogue access of a lane is a whole 4-vector"""
+    return spec.n_out % 4 == 0 and spec.ld_out % 4 == 0 and (not spec.res or spec.ld_res % 4 == 0) and \
+        (not spec.rb or (spec.N + spec.rb_pad) % 4 == 0)
+
+
+def epilogue_paths(spec, plan):
+    """The set of epilogue / reducer paths a launch of `spec` under plan (shape, bn, split) executes."""
+    shape, bn, split = plan
+    if shape == 3:
+        return {"panel"}
+    _, bm, bk, wm, wn = SHAPES[shape]
+    wtn = bn // wn
+    nf = wtn // 16
+    vec = kernel_vec(spec)
+    paths = {f"shape:{SHAPES[shape][0]}/bn{bn}"}
+    if split > 1:                                                     # :614 raw partial tile -> workspace; the reducer (:880-910)
+        paths.add("ws_partial")
+        paths.add("reducer:geglu" if spec.geglu else "reducer:rowbias" if spec.rb else "reducer:plain")   # :901 / :904
+        if spec.res:
+            paths |= {"reducer:residual", "res_unfolded"}             # :907
+        paths.add("reducer:out16" if spec.out16 else "reducer:f32")   # :908-909
+        return paths
+    if spec.res:
+        paths.add("res_folded" if vec and not spec.geglu else "res_unfolded")        # :341
+    c0s = [n0 + w * wtn + ni * 16 for n0 in range(0, spec.N, bn) for w in range(wn) for ni in range(0, nf - 1, 2)]
+    if vec and spec.out16 and spec.ld_out % 8 == 0 and (not spec.geglu or nf % 4 == 0):   # :653 the paired-store loop
+        if not spec.geglu:
+            for c0 in c0s:                                            # :702-707
+                if c0 + 32 <= spec.N:
+                    paths.add("pair16")
+                    if spec.split_out:
+                        paths.add("split_out:pair")                   # :706
+                elif c0 < spec.N:
+                    paths.add("pair_false_live")                      # :679 with a live first fragment
+            if nf % 2 == 1 and any(n0 + w * wtn + (nf - 1) * 16 < spec.N for n0 in range(0, spec.N, bn) for w in range(wn)):
+                paths.add("odd_last_fragment")                        # :708-717 (BN = 160: NF = 5)
+                if spec.split_out:
+                    paths.add("split_out:odd")                        # :713
+        else:
+            paths.add("geglu:pair16")                                 # :719-736
+        return paths
+    if spec.geglu:
+        paths.add("geglu:general")                                    # :829-854 (fp32, or 8-byte 16-bit stores)
+    elif not vec:
+        paths.add("scalar")                                           # :816-826
+    elif spec.out16:
+        paths.add("st8_16")                                           # :814 8-byte 16-bit stores
+    else:
+        paths.add("f32_vector")                                       # :812
+    if spec.cs and vec and not spec.geglu:                            # :751
+        paths.add("cs")
+        if spec.M % CS_ROWS:
+            paths.add("cs_partial_slab")                              # :761 / :795: rows >= M excluded, the slab still live
+    if spec.M % bm == 1 and spec.M > bm:
+        paths.add("second_tile_one_row")
+    return paths
+
+
+REQUIRED_PATHS = {"f32_vector", "scalar", "pair16", "st8_16", "pair_false_live", "odd_last_fragment", "geglu:pair16",
+                  "geglu:general", "res_folded", "res_unfolded", "cs", "cs_partial_slab", "split_out:pair", "split_out:odd",
+                  "ws_partial", "reducer:geglu", "reducer:rowbias", "reducer:plain", "reducer:residual", "reducer:out16",
+                  "reducer:f32", "panel", "second_tile_one_row"}
+REQUIRED_SHAPE_BN = {f"shape:{SHAPES[s][0]}/bn{bn}" for s in (0, 1, 2, 5) for bn in (64, 128, 160)} | {"shape:pp256/bn256"}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# CPU model of the kernels' arithmetic (fp32 torch), with switchable modelled mistakes
+DEFECTS = ("drop_last_ktile", "overlap_ktile", "kykx_transposed", "clamp_pad", "temporal_cross_batch", "rb_tile_first_row",
+           "geglu_swapped", "res_before_gate", "acc16_per_ktile", "ntail_not_stored", "lo_zero")
+
+
+def erf_poly32(x0):
+    """common.h erf_poly: the gate's polynomial erf, fp32, same operation order"""
+    c = (1.128268426e+00, -3.753148778e-01, 1.110793392e-01, -2.510286405e-02, 4.235428536e-03, -5.110371224e-04,
+         4.106055754e-05, -1.944825013e-06, 4.074217005e-08)
+    x = x0.clamp(-3.0, 3.0)
+    u = x * x
+    p = torch.full_like(x, c[8])
+    for k in range(7, -1, -1):
+        p = p * u + c[k]
+    return torch.where(x0.abs() < 3.0, p * x, torch.sign(x0))
+
+
+def model(op, plan=(0, 64, 1), defect=None, gate="erff"):
+    """fp32 model of one launch under plan (shape, bn, split): per-split fp32 accumulation K-tile by K-tile (64 elements),
+    partial planes summed in split order, the epilogue in the ABI's order, one rounding of the output.  Returns (out [M,
+    n_out], lo or None).  gate: "erff" (libm) or "poly" (the kernel's polynomial)."""
+    assert defect is None or defect in DEFECTS, defect
+    sp, dt = op.spec, op.dt
+    bm, split = SHAPES[plan[0]][1], plan[2]
+    gd = defect if defect in ("kykx_transposed", "clamp_pad", "temporal_cross_batch") else None
+    W = _w_terms(op, torch.float32)
+    tiles = []
+    for t, P in enumerate(tap_patches(sp, op.A.float(), gd)):
+        for c in range(0, sp.C1, 64):
+            tiles.append((P[:, c:c + 64], W[:, t * sp.C1 + c:t * sp.C1 + c + 64]))
+    for c in range(0, sp.C2, 64):
+        tiles.append((op.A2.float()[:, c:c + 64], W[:, sp.taps * sp.C1 + c:sp.taps * sp.C1 + c + 64]))
+    KT = len(tiles)
+    total = torch.zeros(sp.M, sp.N)
+    for s in range(split):
+        b, e = KT * s // split, KT * (s + 1) // split
+        if defect == "drop_last_ktile" and s == split - 1:
+            e -= 1
+        if defect == "overlap_ktile" and s > 0:
+            b -= 1
+        acc = torch.zeros(sp.M, sp.N)
+        for a_, w_ in tiles[b:e]:
+            acc = acc + a_ @ w_.t()
+            if defect == "acc16_per_ktile":
+                acc = acc.to(dt).float()
+        total = total + acc
+    v = total
+    if op.bias is not None:
+        v = v + op.bias
+    if op.rowbias is not None:
+        m = torch.arange(sp.M)
+        idx = (m // bm * bm if defect == "rb_tile_first_row" else m) // sp.rb
+        v = v + op.rowbias[idx]
+    if sp.geglu:
+        val, g = _degeglu(v)
+        if defect == "geglu_swapped":
+            val, g = g, val
+        if defect == "res_before_gate" and op.residual is not None:
+            val = val + op.residual
+        erf = erf_poly32(g * 0.70710678118654752440) if gate == "poly" else torch.erf(g * 0.70710678118654752440)
+        h = g * 0.5
+        v = val * (h + h * erf)
+        if op.residual is not None and defect != "res_before_gate":
+            v = v + op.residual
+    elif op.residual is not None:
+        v = v + op.residual
+    out = v if not sp.out16 else v.to(dt)
+    lo = None
+    if sp.split_out:
+        lo = (v - out.float()).to(dt)
+        if defect == "lo_zero":
+            lo = torch.zeros_like(lo)
+    if defect == "ntail_not_stored":                                  # the last 16-column fragment of the N tail keeps what was there
+        out = out.clone()
+        out[:, (sp.n_out - 1) // 16 * 16:] = 0
+    return out, lo
+
+
+def torch_fp32(op):
+    """fp32 torch in ONE matmul per tap (another summation order than the model's K-tiles): the yardstick on the CPU"""
+    sp = op.spec
+    W = _w_terms(op, torch.float32)
+    P = torch.cat(tap_patches(sp, op.A.float()) + ([op.A2.float()] if sp.C2 else []), 1)
+    v = P @ W.t()
+    if op.bias is not None:
+        v = v + op.bias
+    if op.rowbias is not None:
+        v = v + op.rowbias[torch.arange(sp.M) // sp.rb]
+    if sp.geglu:
+        val, g = _degeglu(v)
+        v = val * (0.5 * g * (1.0 + torch.erf(g * 0.70710678118654752440)))
+    if op.residual is not None:
+        v = v + op.residual
+    out = v if not sp.out16 else v.to(op.dt)
+    return out, ((v - out.float()).to(op.dt) if sp.split_out else None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sentinels: a fixed finite bit pattern compared by bits after a launch (norm_cases.sentinel, any shape)
+def sentinel(numel, dt):
+    i = torch.arange(numel, dtype=torch.int64)
+    if dt == torch.float32:
+        return (0x3F800000 + (i * 7919 + 13) % 1021).to(torch.int32).view(torch.float32)
+    return ((0x3C00 if dt == torch.float16 else 0x3F80) + (i * 7919 + 13) % 101).to(torch.int16).view(dt)
+
+
+def out_frame(spec, dt):
+    """(frame [M + 2 GUARD, ldo + 2 col pads], row slice, column slice of the live block).  The launch gets the address of
+    frame[GUARD, col_off] and ldo = the frame's row stride; sentinel rows above and below, sentinel columns left (col_off)
+    and right (ldo > w_out) of the live block."""
+    odt = dt if spec.out16 else torch.float32
+    ld = spec.ld_out
+    assert ld >= spec.col_off + spec.w_out
+    fr = sentinel((spec.M + 2 * GUARD) * ld, odt).view(spec.M + 2 * GUARD, ld)
+    return fr, slice(GUARD, GUARD + spec.M), slice(spec.col_off, spec.col_off + spec.w_out)
+
+
+def frame_violations(before, after, rows, cols):
+    """flat indices outside the live block whose bits changed"""
+    ch = bits(before) != bits(after)
+    ch[rows, cols] = False
+    return ch.flatten().nonzero().flatten().tolist()

@@ -1,0 +1,351 @@
+"""The tap-GEMM (csrc/tapgemm.hip, its split-K reducer) and the panel GEMM (csrc/panelgemm.hip) at tile edges: per-ELEMENT
+parity with an fp64 evaluation of the ABI formula on the same 16-bit operands under the bound derived in tests/gemm_cases.py
+(any summation order of fp32 products; never tuned to what a GPU gives), BIT equality on small-integer operands, every legal
+(block shape, BN, split-K) of every case through the product ABI's plan table, dead storage poisoned with NaN, outputs /
+column statistics / split-K workspace framed by sentinels.
+
+CPU tests (unmarked): every family has its property at every shape used and fp32 torch sits inside the bound (bit-equal on
+integers); eleven modelled mistakes are each CAUGHT on the case built for them while the same model without the mistake
+passes; one K-tile dropped from one row of a conv_big-sized launch passes the whole-tensor rel-L2 of the older tests and leaves
+the bound by orders; the case table reaches every streaming shape x BN, every epilogue path of tapgemm_kernel and every
+reducer branch.  GPU tests: the real kernels.  Measured values: DESIGN.md section 3.1, profiles/tapgemm_edges_parity.json."""
+import ctypes as C
+import math
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gemm_cases as gc  # noqa: E402
+
+DEV = "cuda:0"
+ALL = sorted(gc.SPECS)
+
+
+# ---- the launch description of a case, on any device ---------------------------------------------------------------------
+def _tap(op, dev, out=None):
+    """vgen_amd.ops.TapGemm of `op` with every operand a view into its NaN-poisoned storage on `dev`."""
+    from vgen_amd import lib as L
+    from vgen_amd.ops import TapGemm
+    sp = op.spec
+
+    def live(store, view):
+        if view is None:
+            return None
+        if store is None:
+            return view.to(dev)
+        return torch.as_strided(store.to(dev), view.shape, view.stride(), view.storage_offset())
+    W = live(op.W_store, op.W)
+    if sp.dualw:
+        hi = op.W_hi.to(dev)
+        hi.vgen_dw = W
+        W = hi
+    kw = dict(A=live(op.A_store, op.A), W=W, M=sp.M, N=sp.N, C1=sp.C1, taps=sp.taps, C2=sp.C2, A2=live(op.A2_store, op.A2),
+              bias=live(None, op.bias), rowbias=live(op.rb_store, op.rowbias), rows_per_rb=sp.rb,
+              residual=live(op.res_store, op.residual), out_dtype=op.dt if sp.out16 else torch.float32,
+              epilogue=L.EPI_GEGLU if sp.geglu else L.EPI_NONE, colstats=sp.cs, split_out=sp.split_out, out=out)
+    if sp.mode == "conv":
+        nimg, Hi, Wi, Ho, Wo, stride, pad, ups, crop = sp.geom
+        kw.update(mode=L.TAP_CONV3X3, Hi=Hi, Wi=Wi, Ho=Ho, Wo=Wo, stride=stride, pad_t=pad, pad_l=pad, ups=ups, crop_t=crop)
+    elif sp.mode == "temp":
+        kw.update(mode=L.TAP_TEMPORAL3, F=sp.geom[1], S=sp.geom[2])
+    return TapGemm(**kw)
+
+
+def _signature(g):
+    from vgen_amd.ops import _ENUM
+    flags = (1 if g.residual is not None else 0) | (2 if g.rowbias is not None else 0) | (4 if g.colstats else 0)
+    return [g.mode, g.M, g.N, g.C1, g.C2, g.taps, g.epilogue, _ENUM[g.out_dtype], flags]
+
+
+class _Installed:
+    """One row in the plan table of the product ABI (vgen_tapgemm_set_plans); the compiled-in table comes back on exit."""
+    def __init__(self, be, g, plan):
+        self.be, self.row = be, (C.c_int64 * 12)(*(_signature(g) + list(plan)))
+
+    def __enter__(self):
+        assert self.be.lib.vgen_tapgemm_set_plans(self.row, 1) == 0
+        return self
+
+    def __exit__(self, *exc):
+        self.be.lib.vgen_tapgemm_set_plans(None, -1)
+        return False
+
+
+def legal_plans(be, g, spec):
+    """[(plan, tabled)]: the planner's own choice first, then every (streaming shape, BN, split in {1, 2, spec.splits,
+    largest}) that the planner CONFIRMS when it is installed as a table row (vgen_tapgemm_query_plan returns the row).  Needs
+    no GPU.  Dual-W launches never read the table: their own plan only."""
+    own = tuple(be.tapgemm_plan(g))
+    plans = [(own, False)]
+    if not spec.sweep or spec.dualw:
+        return plans
+
+    def confirmed(plan):
+        with _Installed(be, g, plan):
+            return tuple(be.tapgemm_plan(g)) == plan
+    for shape in gc.STREAMING:
+        for bn in gc.BNS:
+            # pp256 takes fp32 outputs through split-K only: split 1 may be illegal where split 2 is not
+            largest = next((s for s in range(32, 0, -1) if confirmed((shape, bn, s))), 0)
+            for s in sorted({1, 2, largest} | set(spec.splits)):
+                if 0 < s <= largest and (shape, bn, s) != own and confirmed((shape, bn, s)):
+                    plans.append(((shape, bn, s), True))
+    return plans
+
+
+@pytest.fixture(scope="module")
+def host_be():
+    from vgen_amd import ops
+    return ops.HipBackend()          # loads the library; plan queries launch nothing
+
+
+# ---- CPU: families, reference, fp32 torch inside the bound ------------------------------------------------------------------
+@pytest.mark.parametrize("name", ALL)
+def test_family_properties_and_torch_fp32_inside_the_bound(name):
+    """Every (family, dtype) of the case: the family has its property (and the poison is where it should be); fp32 torch — one
+    matmul, another summation order than any kernel's — is inside the bound, bit-equal on integers; so is the K-tile model."""
+    sp = gc.SPECS[name]
+    for fam in gc.FAMILIES:
+        for dtn, dt in gc.DTS.items():
+            op = gc.operands(sp, fam, dt)
+            gc.family_property(op)
+            ref = gc.reference(op)
+            for what, (out, lo) in (("torch", gc.torch_fp32(op)), ("model", gc.model(op, (0, 64, 1 if sp.K < 512 else 2)) if sp.K <= 4096 else (None, None))):
+                if out is None:
+                    continue
+                w, bad, msgs = gc.check(op, ref, out, lo)
+                assert w <= 1, (name, fam, dtn, what, w, msgs, gc.offenders(op, ref, out, bad, (0, 64, 1)))
+                if fam == "scaled" and not sp.out16:        # not vacuous, and far from tight: fp32 rounding errors are centred
+                    assert 0 < w < 0.2, (name, dtn, what, w)
+
+
+def test_a_degenerate_family_is_noticed():
+    sp = gc.SPECS["lin_300x320x192_rb7"]
+    op = gc.operands(sp, "gauss", torch.bfloat16)
+    for fam in gc.FAMILIES:
+        op.family = fam
+        with pytest.raises(AssertionError):
+            gc.family_property(op)
+
+
+def test_the_kernels_polynomial_gate_is_inside_the_bound():
+    """tapgemm's GEGLU gate is common.h's erf polynomial (2.2e-5 absolute on erf), not libm's erff whose 16 ulp the bound
+    prices: the fp32 part of value and gate, (K + 4) 2^-23 sum |a| |w|, covers it at every GEGLU case of the table."""
+    worst = 0.0
+    for name, sp in gc.SPECS.items():
+        if not sp.geglu:
+            continue
+        for dt in gc.DTS.values():
+            op = gc.operands(sp, "scaled", dt)
+            out, _ = gc.model(op, (0, 64, 1), gate="poly")
+            w = gc.check(op, gc.reference(op), out)[0]
+            assert w <= 1, (name, dt, w)
+            if not sp.out16:
+                worst = max(worst, w)
+    print(f"polynomial gate, fp32 outputs: worst / bound {worst:.3f}")
+    assert 0.05 < worst < 0.7
+
+
+# ---- CPU: the modelled mistakes ----------------------------------------------------------------------------------------------
+DEFECT_CASES = [("drop_last_ktile", "conv_C192_KT27", (0, 128, 3)), ("overlap_ktile", "conv_C192_KT27", (0, 128, 3)),
+                ("kykx_transposed", "conv_3x5_nimg7_rb15", (0, 128, 1)), ("clamp_pad", "conv_s2p1_7x5", (0, 64, 1)),
+                ("temporal_cross_batch", "temp_3x5x24", (0, 128, 1)), ("rb_tile_first_row", "lin_300x320x192_rb7", (0, 160, 1)),
+                ("geglu_swapped", "geglu_130x64_f32", (0, 64, 1)), ("res_before_gate", "geglu_130x128_out16_res", (0, 128, 1)),
+                ("acc16_per_ktile", "conv_C192_KT27", (0, 128, 1)), ("ntail_not_stored", "lin_129x80x192_out16", (0, 64, 1)),
+                ("lo_zero", "splitout_130x96", (0, 64, 1))]
+
+
+@pytest.mark.parametrize("dtname", ["bf16", "fp16"])
+@pytest.mark.parametrize("defect,name,plan", DEFECT_CASES, ids=lambda v: v if isinstance(v, str) else "x".join(map(str, v)))
+def test_modelled_mistake_is_caught(dtname, defect, name, plan):
+    """Acceptance test of the metric: each modelled mistake leaves the bound on `scaled` AND breaks bit equality on
+    `int_exact`, on the case built for it; the same model without the mistake passes both."""
+    assert set(d for d, _, _ in DEFECT_CASES) == set(gc.DEFECTS)
+    for fam in gc.FAMILIES:
+        op = gc.operands(gc.SPECS[name], fam, gc.DTS[dtname])
+        ref = gc.reference(op)
+        ok = gc.check(op, ref, *gc.model(op, plan))[0]
+        bad = gc.check(op, ref, *gc.model(op, plan, defect=defect))[0]
+        print(f"{defect} on {name} {fam} {dtname}: worst {ok:.3g} -> {bad:.3g}")
+        if fam == "int_exact" and (defect == "acc16_per_ktile" or (defect, dtname) == ("lo_zero", "fp16")):
+            continue            # integers of this size are exact in 16 bits (fp16: up to 2048 > 9 K): `scaled` is the family here
+        assert ok <= 1 < bad, (defect, fam, ok, bad)
+
+
+def test_one_ktile_missing_from_one_row_passes_the_whole_tensor_rel_l2():
+    """Why this file exists.  conv_big of the older tests: 7168 rows, K = 2880 (45 K-tiles), an fp32 residual of the product's
+    size, Gaussian operands.  One K-tile missing from ONE row moves the rel-L2 of a bf16 launch's fp32 output to ~1.2e-3 —
+    under kernel_cases.TOL16_EMU["bf16"], the limit the older tests hold 16-bit-operand launches to — while the per-element
+    statistic goes from 1e-4 to 35 (the bound grows with K: (K + 4) 2^-23 of sum |a| |w| is generous at K = 2880)."""
+    import kernel_cases as kc
+    sp = gc.conv("conv_big", 4, 32, 56, 32, 56, 320, 320, res=True)
+    assert (sp.M, sp.K, sp.K // 64) == (7168, 2880, 45)
+    op = gc.operands(sp, "gauss", torch.bfloat16)
+    ref = gc.reference(op)
+    good, _ = gc.torch_fp32(op)
+    row, kt = 4321, 17
+    P = gc.tap_patches(sp, op.A.float())[kt // 5]
+    c = kt % 5 * 64
+    bad = good.clone()
+    bad[row] -= P[row, c:c + 64] @ op.W.float()[:, kt * 64:(kt + 1) * 64].t()
+    rl = lambda o: float((o.double() - ref.ref).norm() / ref.ref.norm())      # noqa: E731
+    wg, wb = gc.check(op, ref, good)[0], gc.check(op, ref, bad)[0]
+    # the same mistake in EVERY row would be sqrt(7168) = 85 x larger in rel-L2: what one row contributes is 1 / 85 of it
+    print(f"rel-L2 {rl(good):.2e} -> {rl(bad):.2e} (limit {kc.TOL16_EMU['bf16']:.0e}); worst / bound {wg:.3g} -> {wb:.3g}")
+    assert rl(good) < 1e-6 and 5e-4 < rl(bad) <= kc.TOL16_EMU["bf16"]
+    assert wg <= 1 and wb > 10
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16, torch.float32], ids=str)
+def test_sentinel_frame_reports_a_stray_store(dt):
+    sp = gc.Spec("frame", 5, 12, 64, out16=dt != torch.float32, ldo=20, col_off=4)
+    fr, rows, cols = gc.out_frame(sp, dt if dt != torch.float32 else torch.bfloat16)
+    assert fr.dtype == dt and bool(torch.isfinite(fr.float()).all())
+    after = fr.clone()
+    after[rows, cols] = 0
+    assert not gc.frame_violations(fr, after, rows, cols)
+    for r, c in ((gc.GUARD - 1, 5), (gc.GUARD, 3), (gc.GUARD + 2, 16), (gc.GUARD + 5, 4), (0, 0)):
+        b2 = after.clone()
+        gc.bits(b2)[r, c] ^= 1
+        assert gc.frame_violations(fr, b2, rows, cols) == [r * 20 + c]
+
+
+# ---- CPU: what the table reaches ---------------------------------------------------------------------------------------------
+def test_case_table_reaches_every_shape_path_and_reducer_branch(host_be):
+    """Every (case, plan) pair the GPU test runs, asked of the library's planner: each streaming shape with each BN it takes,
+    each epilogue path of tapgemm_kernel (gemm_cases.epilogue_paths cites the kernel's lines), each reducer branch, the panel
+    shape, both dual-W shapes, the K edges of the issue."""
+    paths, pairs, by_spec = set(), 0, {}
+    for name, sp in gc.SPECS.items():
+        op = gc.operands(sp, "int_exact", torch.bfloat16)
+        plans = legal_plans(host_be, _tap(op, "cpu"), sp)
+        by_spec[name] = [p for p, _ in plans]
+        assert len(set(by_spec[name])) == len(plans)
+        pairs += len(plans)
+        for p, _ in plans:
+            paths |= gc.epilogue_paths(sp, p)
+    missing = (gc.REQUIRED_PATHS | gc.REQUIRED_SHAPE_BN) - paths
+    print(f"{len(gc.SPECS)} cases, {pairs} (case, plan) pairs, {len(paths)} distinct paths")
+    assert not missing, sorted(missing)
+    assert pairs >= 4 * len(gc.SPECS)
+    # panel: the planner's own choice for every panel case, in every panel width
+    assert all(by_spec[n][0][0] == 3 for n in gc.PANEL_NAMES), {n: by_spec[n][0] for n in gc.PANEL_NAMES}
+    assert {by_spec[n][0][1] for n in gc.PANEL_NAMES} == {80, 160}
+    # ... and the plan table takes the non-dual-W ones away from it, onto every streaming shape
+    assert all(len(by_spec[n]) > 4 for n in gc.PANEL_NAMES if gc.SPECS[n].sweep)
+    # dual-W: the planner's own choice, both ping-pong shapes and the panel
+    assert {by_spec[n][0][0] for n in gc.DUALW_NAMES} == {0, 2, 3}, {n: by_spec[n][0] for n in gc.DUALW_NAMES}
+    assert any(by_spec[n][0][2] > 1 for n in gc.DUALW_NAMES)
+    # split-K: the issue's factors, boundaries mid-tap and on the segment edge
+    for n in ("splitk_f32", "splitk_out16", "splitk_rb", "splitk_res", "splitk_geglu"):
+        assert {p[2] for p in by_spec[n]} >= {1, 2, 3, 4}, (n, by_spec[n])
+    assert {p[2] for p in by_spec["conv_C192_KT27"]} >= {1, 2, 3, 4, 5, 6}
+    assert any(27 * s // k % 3 for k in range(2, 7) for s in range(1, k))                # 3 K-tiles per tap: a cut inside a tap
+    assert {p[2] for p in by_spec["conv_C64_KT9"]} >= {1, 2} and {p[2] for p in by_spec["temp_C192_split2"]} >= {1, 2}
+    for n, c1 in (("seg_100x128_256+320", 256), ("seg_100x128_320+256", 320)):
+        assert any(p[2] == 2 for p in by_spec[n])
+        assert (9 // 2 == c1 // 64) == (c1 == 256)                                       # cut at K-tile 4: the edge / inside segment 1
+    # K of one, two and three ring stages on the BK = 32 shapes
+    for n, k in (("lin_100x128x64_K1tile", 64), ("lin_100x128x128_K2tiles", 128), ("lin_100x64x192_K3tiles", 192)):
+        assert gc.SPECS[n].K == k and {p[0] for p in by_spec[n]} >= {1, 5}
+    # the K limit
+    assert gc.SPECS["limit_2x4xK131008"].K * 2 == 262144 - 128 and gc.SPECS["dw_limit_2x4xK65472"].K * 4 <= 262144 - 128
+
+
+# ---- GPU -----------------------------------------------------------------------------------------------------------------------
+def _record(key, val):
+    from test_gpu_model import _record as rec
+    rec(key, val)
+
+
+def _run(be, op, ref, plan, tabled):
+    """One launch of `op` under `plan` through the C ABI: output into a sentinel frame, column statistics and split-K
+    workspace into sentinel-tailed buffers (the workspace pre-filled with NaN).  Returns (worst, failure messages)."""
+    from vgen_amd import lib as L
+    sp, dt = op.spec, op.dt
+    tag = f"{sp.name} {op.family} {str(dt)[6:]} plan {plan}"
+    fr0, rows, cols = gc.out_frame(sp, dt)
+    frd = fr0.to(DEV)
+    g = op.dev_tap                    # the operands were uploaded once per (case, dtype, family)
+    g.out = frd[rows, cols]
+    fails = []
+
+    def launch():
+        got = tuple(be.tapgemm_plan(g))
+        assert got == plan, (tag, "planner answers", got)
+        a, _, _, _, _, _, _, _, _keep = be._tapgemm_args(g)
+        need = be.lib.vgen_tapgemm_ws_bytes(C.byref(a))
+        assert (need > 0) == (plan[2] > 1) and need == (plan[2] * sp.M * sp.N * 4 if plan[2] > 1 else 0), (tag, need)
+        ws0 = torch.cat([torch.full((need // 4,), float("nan")), gc.sentinel(64, torch.float32)])
+        wsd = ws0.to(DEV)
+        a.ws, a.ws_bytes = (wsd.data_ptr(), need) if need else (None, 0)
+        ncs = (sp.M + gc.CS_ROWS - 1) // gc.CS_ROWS * 2 * sp.N if sp.cs else 0
+        cs0 = gc.sentinel(ncs + 128, torch.float32)
+        csd = cs0.to(DEV)
+        if sp.cs:
+            a.colstats = csd.data_ptr() + 64 * 4
+        rc = be.lib.vgen_tapgemm(C.byref(a), C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream))
+        L.check(rc, "vgen_tapgemm")
+        torch.cuda.synchronize()
+        return wsd.cpu(), ws0, csd.cpu(), cs0, ncs, need
+
+    if tabled:
+        with _Installed(be, g, plan):
+            ws1, ws0, cs1, cs0, ncs, need = launch()
+    else:
+        ws1, ws0, cs1, cs0, ncs, need = launch()
+    fr1 = frd.cpu()
+    live = fr1[rows, cols]
+    out, lo = (live[:, :sp.n_out], live[:, sp.n_out:]) if sp.split_out else (live, None)
+    w, bad, msgs = gc.check(op, ref, out, lo)
+    if not w <= 1:
+        fails.append(f"{tag}: worst / bound {w:.3g}\n" + "\n".join(msgs + [gc.offenders(op, ref, out, bad, plan)]))
+    v = gc.frame_violations(fr0, fr1, rows, cols)
+    if v:
+        fails.append(f"{tag}: sentinels around the output written at (row, col) {[divmod(i, fr0.shape[1]) for i in v[:10]]} ({len(v)})")
+    if not torch.equal(gc.bits(ws1[need // 4:]), gc.bits(ws0[need // 4:])):
+        fails.append(f"{tag}: sentinel tail of the split-K workspace written")
+    if sp.cs:
+        wc, m2 = gc.check_colstats(sp, out, cs1[64:64 + ncs].view(-1, 2, sp.N), exact=op.family == "int_exact")
+        if not wc <= 1:
+            fails.append(f"{tag}: " + "; ".join(m2))
+        w = max(w, wc) if op.family == "scaled" else w
+        edge = torch.cat([gc.bits(cs1[:64]) != gc.bits(cs0[:64]), gc.bits(cs1[64 + ncs:]) != gc.bits(cs0[64 + ncs:])])
+        if bool(edge.any()):
+            fails.append(f"{tag}: sentinels around the column statistics written")
+    flips = int((gc.bits(out) != gc.bits(gc.r16(ref.ref, dt))).sum()) if sp.out16 and op.family == "scaled" else 0
+    return w, fails, flips
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ALL)
+def test_tapgemm_per_element_on_device(hip_backend, name):
+    """One case: both dtypes x both families x every legal plan.  `scaled` within the bound per element against fp64;
+    `int_exact` bit-equal (output, split_out lo, column statistics); no sentinel moved; outputs finite although every dead
+    row and column of A, W, the row bias and the residual is NaN."""
+    sp = gc.SPECS[name]
+    fails, worst, flips, nrun = [], {}, {}, 0
+    for dtn, dt in gc.DTS.items():
+        for fam in gc.FAMILIES:
+            op = gc.operands(sp, fam, dt)
+            ref = gc.reference(op)
+            op.dev_tap = _tap(op, DEV)
+            plans = legal_plans(hip_backend, op.dev_tap, sp)
+            for plan, tabled in plans:
+                w, f, nf = _run(hip_backend, op, ref, plan, tabled)
+                nrun += 1
+                fails += f
+                if fam == "scaled":
+                    worst[dtn] = max(worst.get(dtn, 0.0), w)
+                    flips[dtn] = max(flips.get(dtn, 0), nf)
+    for dtn, w in worst.items():
+        print(f"tapgemm_edges/{name}/{dtn}: worst / bound {w:.4f} over {nrun // 4} plans")
+        _record(f"tapgemm_edges/{name}/{dtn}", round(w, 4) if math.isfinite(w) else str(w))
+        if sp.out16:        # a 16-bit output inside its interval reaches 1.0 by its own rounding; what tells launches apart is
+            # how many elements are NOT the rounding of the fp64 value itself, i.e. used some of e32 (the most over the plans)
+            _record(f"tapgemm_edges/{name}/{dtn}/not_r16_of_ref", f"{flips[dtn]} of {sp.M * sp.n_out}")
+    _record(f"tapgemm_edges/{name}/launches", nrun)
+    assert not fails, "\n".join(fails[:20]) + (f"\n... {len(fails)} failures" if len(fails) > 20 else "")
